@@ -3,6 +3,12 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config B|C|D|E] [--frames F]
                     [--exchange] [--backend nccl|gloo] [--batches R] [--streams S]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs is given, and prints the headline's JSON line.  Everything else described below
+that takes runs of its own (`roofline`'s kernel timing and copy ceiling, `host_inclusive`,
+`namespace_exchange`, config D's `alternative`, `cpu_baseline`) is measured with --full.
 
 A step = one batch through the hot path: emurx_classify_dev = one k_rx launch (decode +
 checksums + Namespace/Client lookups + 32-B records + stable per-callback queue segments +
@@ -18,7 +24,7 @@ instead of waiting for its last workgroups.  Warmup runs --warmup steps and then
 until --warmup-seconds of wall time have passed (settled clocks for short runs).  For N > 1
 (torchrun, one rank per GPU) every rank processes its own F-frame shard against replicated
 tables: frames are independent, so there is no data-path collective (weak scaling); value =
-frames over all ranks / max-over-ranks time.  At every N (N = 1 included) the Namespace-owner
+frames over all ranks / max-over-ranks time.  With --full, at every N (N = 1 included) the Namespace-owner
 exchange (config D, 2M frames per GPU, partitioned tables) is timed beside it with the same steps
 and warmup (`namespace_exchange`); at N > 1 rank 0 also times its N = 1 twin in the same job
 (`namespace_exchange.exchange_scaling_target`: the >= 6x-at-8-GPUs target of the north star).
@@ -28,7 +34,7 @@ Namespace-partitioned exchange to every step: emurx_parse_route_dev packs every 
 lookup record into its Namespace owner's region, an all-to-all (RCCL over xGMI) delivers the
 regions, with the per-region counts in a second all-to-all, and the owner resolves them.
 
-The JSON line carries `roofline` (algorithmic bytes per frame = frame_len + 8 B descriptor
+With --full the JSON line carries `roofline` (algorithmic bytes per frame = frame_len + 8 B descriptor
 + 32 B record + 4 B queue entry, over k_rx's duration with each launch alone: the same --steps
 launches back to back on one stream over the rotating slots, one HIP event pair around them;
 `roofline.pipelined` is the launch interval on the S streams of a second region of the same
@@ -56,6 +62,15 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything the line carried beside its headline: the per-launch, launch-interval and "
+                         "cache-resident figures and the copy ceiling of `roofline`, `host_inclusive`, "
+                         "`namespace_exchange` (config D's `alternative`) and `cpu_baseline`.  Without it a run sets "
+                         "up, warms up, times the steps and prints the headline's line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step's emurx_classify_dev call returned "
+                         "to DIR/<name>.npy (float32 / float64; see dump_outputs); the inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
     ap.add_argument("--config", default="B", choices=["B", "C", "D", "E"])
     ap.add_argument("--frames", type=int, default=None,
                     help="frames per GPU per step (default 1M; config D: 2M = 16M over 8 GPUs)")
@@ -78,16 +93,17 @@ def parse_args():
     ap.add_argument("--exchange-frames", type=int, default=1 << 21,
                     help="frames per GPU of the config-D Namespace-exchange measurement beside the headline")
     ap.add_argument("--no-exchange-run", action="store_true",
-                    help="skip the config-D Namespace-exchange measurement beside the config-B headline")
+                    help="--full: skip the config-D Namespace-exchange measurement beside the config-B headline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the multi-rank path with ranks sharing a GPU")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--time-stride", type=int, default=4,
                     help="record HIP events around every N-th launch of the timing pass (the timed region's steps once "
                          "more, after it)")
-    ap.add_argument("--kernel-timing", default="region", choices=["region", "launch", "off"],
-                    help="steps that are one k_rx launch (no exchange): region = an event pair per stream around "
+    ap.add_argument("--kernel-timing", default=None, choices=["region", "launch", "off"],
+                    help="steps that are one k_rx launch (no exchange; default: region with --full, else off): "
+                         "region = an event pair per stream around "
                          "a second region of the same steps (the launch interval) and one around launches "
                          "back to back on one stream (each launch alone); launch = events around every "
                          "--time-stride-th launch of a timing pass; off = wall clock only")
@@ -114,7 +130,7 @@ def parse_args():
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous + max-over-ranks reduction only, no GPU (CPU test of the launch path)")
     ap.add_argument("--no-host-inclusive", action="store_true",
-                    help="skip the default line's bounded host-inclusive block (every N)")
+                    help="--full: skip the line's bounded host-inclusive block (every N)")
     ap.add_argument("--ingest-slots", type=int, default=2,
                     help="ingest slots the host-inclusive passes rotate through (one filled while the others "
                          "are in flight; at most EMURX_INGEST_SLOTS; 3 and 4 measured slower, DESIGN.md §6)")
@@ -127,7 +143,10 @@ def parse_args():
                     help="N > 1 with an exchange: after the timed steps, run 4 more overlapped steps and write "
                          "every rank's received and resolved records per step, and its input batches, to DIR "
                          "(tests/test_bench_launch.py checks them against the oracle)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.kernel_timing is None:
+        a.kernel_timing = "region" if a.full else "off"
+    return a
 
 
 def workload(cfg, n, rank):
@@ -292,6 +311,9 @@ def main():
     if a.frames is None:
         a.frames = (1 << 21) if a.config == "D" else (1 << 20)
     mode = a.tables or ("partitioned" if a.config == "D" or a.exchange else "none")
+    if a.dump_outputs and mode != "none":
+        sys.exit("--dump-outputs covers the steps that are one emurx_classify_dev call (--tables none); the exchange's "
+                 "records are written by --dump-exchange")
     local = local % max(torch.cuda.device_count(), 1)  # gloo rehearsal: ranks may share a GPU
     torch.cuda.set_device(local)
     if world > 1:
@@ -300,7 +322,7 @@ def main():
         else:
             dist.init_process_group("gloo")
     out, rx, w = measure(a, a.config, a.frames, mode, a.steps, a.warmup, rank, world, local, dist, torch)
-    if a.config == "B" and not a.no_host_inclusive and not a.host_path:
+    if a.full and a.config == "B" and not a.no_host_inclusive and not a.host_path:
         # the north star's host-in / host-out rate, at every N (each rank through its own two
         # ingest slots, the node's aggregate): bounded to ~2 s, on the headline's handle
         try:
@@ -310,7 +332,7 @@ def main():
             out["host_inclusive"] = {"error": repr(e)[:300]}
     if a.host_path:
         out["host_inclusive"] = host_path_rate(rx, w, slots=a.ingest_slots)
-    if a.config == "D" and not a.no_exchange_run:
+    if a.full and a.config == "D" and not a.no_exchange_run:
         # SURVEY.md §8e asks for both: the Namespace-partitioned lookups (the headline of D)
         # and the "replicas only" alternative (every GPU holds every table)
         other = "replicated" if mode == "partitioned" else "partitioned"
@@ -322,7 +344,7 @@ def main():
             out["alternative"]["k_rx_ms_mean"] = xo["roofline"]["kernel_ms_mean"]
         except Exception as e:  # noqa: BLE001 - report, keep the headline line
             out["alternative"] = {"error": repr(e)[:300]}
-    if a.config == "B" and not a.no_exchange_run:
+    if a.full and a.config == "B" and not a.no_exchange_run:
         # The Namespace-owner exchange (MapNsT / GetNs thread_ctx.go:139,772-784
         # split over the GPUs), measured at EVERY N with the headline's steps and warmup: config
         # D, 2M frames per GPU, partitioned tables, lookup records all-to-all'd to the owners.
@@ -348,7 +370,7 @@ def main():
         out["tx_checksum"] = tx_csum_rate(rx, w, torch)
     if a.table_updates and rank == 0:
         out["table_updates"] = table_update_cost(a, rx, w, torch)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w, a.cpu_seconds)
         if "host_inclusive" in out and a.config == "B" and "batch_latency_by_msgs" in out["host_inclusive"]:
             out["host_inclusive"]["crossover"] = crossover(out["host_inclusive"], out["cpu_baseline"]["value"])
@@ -814,7 +836,7 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
         t_w = time.perf_counter()
         more = warmup > 0
         while more:
-            for _ in range(max(R, 16)):
+            for _ in range(-(-16 // R) * R):  # whole rotations: the timed steps' slots do not depend on the rounds
                 step()
             torch.cuda.synchronize()
             go = torch.tensor([int(time.perf_counter() - t_w < a.warmup_seconds)], dtype=torch.int64)
@@ -944,6 +966,14 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
     el = time.perf_counter() - t0
     if world > 1:
         dist.barrier()
+    snap = None
+    if a.dump_outputs and xch is None and steps > 0:
+        # --dump-outputs: the last timed step's outputs, copied on the device before any later
+        # pass launches again (written at the end: converting them is host work)
+        j = (kk[0] - 1) % R
+        snap = dict(slot=j, batches=kk[0], rec=outs[j][0].clone(), qlist=outs[j][1].clone(),
+                    tile_cnt=outs[j][2].clone(), hist=hist.clone())
+        torch.cuda.synchronize()
     if not a.no_check and warmup == 0 and steps > 0:  # no warmup: check the timed steps' outputs
         sanity()
     interval = None
@@ -1030,17 +1060,22 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
     # DN = --tables none, DR = replicated)
     tag = cfg + ({"none": "N", "replicated": "R"}.get(mode, "") if cfg == "D" else "")
     pmc = ROOT / "profiles" / f"pmc_config{tag}.json"
-    if pmc.exists():
+    # the roofline block takes runs of its own (the kernel timing passes above, the copy ceiling):
+    # a run without --full or an explicit --kernel-timing leaves it out of the line
+    roof = xch is not None or a.full or a.kernel_timing != "off"
+    if roof and pmc.exists():
         try:
             traffic = json.loads(pmc.read_text()).get("k_rx_hbm_bytes_per_launch")
             pmc_src = str(pmc.relative_to(ROOT))
         except Exception:  # noqa: BLE001
             traffic = None
-    copy_gbs = copy_ceiling(torch, dev, stream)
+    copy_gbs = copy_ceiling(torch, dev, stream) if roof else 0.0
     # the Namespace + Client bucket reads of every frame that reaches a callback (two 64-B
     # buckets, issued together): outside the algorithmic bytes, served by L2 / MALL / HBM
-    r = rec.cpu().numpy().view(abi.REC_DTYPE)
-    probed = int((r["status"] == 0).sum()) if mode != "partitioned" else 0
+    probed = 0
+    if roof and mode != "partitioned":
+        r = rec.cpu().numpy().view(abi.REC_DTYPE)
+        probed = int((r["status"] == 0).sum())
     ts = rx.table_stats()
     par = {"none": f"frame shards x{world}, replicated tables, no collective",
            "replicated": f"frame shards x{world}, replicated tables, classified records to the Namespace "
@@ -1108,6 +1143,8 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
         "warmup_seconds": round(warm_s, 3),
         "host_submit_ms_per_step": round(t_submit / steps * 1e3, 5),
     }
+    if not roof:
+        del out["roofline"]
     if interval is not None:
         out["roofline"]["pipelined"] = {
             "interval_ms": round(interval, 5), "achieved": round(alg_bytes / (interval * 1e-3) / 1e9, 1),
@@ -1116,7 +1153,7 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
                       f"{S} streams (no cross-stream waits), earliest start to latest end / launches = the launch "
                       "interval in steady state (each launch overlaps its neighbours); the wall-timed region itself "
                       "carries no events"}
-    if mode == "none" and cfg == "D" and world == 1 and pmc.exists():
+    if roof and mode == "none" and cfg == "D" and world == 1 and pmc.exists():
         # D classification (k_rx probing 1.75 GB of sparse tables) against the random-line bound,
         # as the owner's k_lookup: the excess FETCH of the calibrated PMC is probe lines
         # (pmc_summary.py's rule for this config), per launch, at the measured random-line rate of an
@@ -1221,7 +1258,51 @@ def measure(a, cfg, n, mode, steps, warmup, rank, world, local, dist, torch):
                 one["without_key_derivation"] = {"value": one["value"], "ms_per_step": one["ms_per_step"]}
                 ms1 = one["ms_per_step"] + key_ms
                 one["value"], one["ms_per_step"] = round(n * world / (ms1 * 1e-3) / 1e6, 2), round(ms1, 4)
+    if snap is not None:
+        out["outputs_dumped"] = dump_outputs(a.dump_outputs, snap, n, qcap, rank, world)
     return out, rx, w
+
+
+def dump_outputs(d, snap, n, qcap, rank, world, sample=1 << 17, queue_sample=1 << 21):
+    """--dump-outputs: what the last timed step's emurx_classify_dev call handed its caller, as
+    DIR/<name>.npy (at N > 1 every rank writes its own, <name>_rank<r>.npy):
+      records        one row per frame, one float64 column per field of the 32-byte record
+                     (abi.REC_DTYPE's order); at most `sample` frames, a seeded choice of the batch's
+      record_rows    those frames' indices in the batch
+      queues         the frame indices in queue order (the per-tile queue segments packed with
+                     the tile counts, as emurx_rx_stream packs them); past `queue_sample` entries
+                     a seeded choice of positions, listed in queue_rows
+      queue_offsets  queue q = queues[queue_offsets[q]:queue_offsets[q + 1]]
+      histogram      the folded outcome histogram's share of one batch: the device histogram
+                     accumulates over every batch since the handle was opened (the warmup's
+                     length varies with --warmup-seconds), and every batch slot holds the same
+                     frames, so the total over the batches launched is the last step's part
+    The batch slot of the last timed step follows from --warmup, --steps and --batches alone,
+    and the workload and its permutations are seeded: same arguments, same arrays."""
+    import numpy as np
+    from emurx import abi
+    from emurx.rx import hist_fold, pack_queues
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(0x0D0E)
+    rec = snap["rec"].cpu().numpy()[: n * 32].view(abi.REC_DTYPE)
+    rows = np.sort(rng.choice(n, sample, replace=False)) if n > sample else np.arange(n)
+    arrays = {"records": np.stack([rec[k][rows].astype(np.float64) for k in abi.REC_DTYPE.names], axis=1),
+              "record_rows": rows.astype(np.float64)}
+    packed, qoff = pack_queues(snap["qlist"].cpu().numpy(), qcap, snap["tile_cnt"].cpu().numpy(), n)
+    if len(packed) > queue_sample:
+        pos = np.sort(rng.choice(len(packed), queue_sample, replace=False))
+        arrays["queue_rows"] = pos.astype(np.float64)
+        packed = packed[pos]
+    arrays["queues"] = packed.astype(np.float64)
+    arrays["queue_offsets"] = qoff.astype(np.float64)
+    fold = hist_fold(snap["hist"].cpu().numpy().view(np.uint64))
+    arrays["histogram"] = fold.astype(np.float64) / snap["batches"]
+    tail = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(d / f"{name}{tail}.npy", arr)
+    return {"dir": str(d), "batch_slot": snap["slot"], "arrays": sorted(arrays),
+            "bytes": int(sum(v.nbytes for v in arrays.values()))}
 
 
 def a2a_choice_block(res, k_steps):

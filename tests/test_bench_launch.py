@@ -81,7 +81,7 @@ def test_two_rank_exchange_fields(gpu_ok):
     """The bench's N = 2 line over gloo (both ranks on the one GPU): the config-B headline plus the
     Namespace-partitioned exchange timed with the headline's steps and warmup, its per-phase
     device times and the bytes that crossed to the other rank."""
-    p = run(["--gpus", "2", "--backend", "gloo", "--frames", "65536", "--exchange-frames", "65536",
+    p = run(["--full", "--gpus", "2", "--backend", "gloo", "--frames", "65536", "--exchange-frames", "65536",
              "--steps", "6", "--warmup", "2", "--batches", "2", "--warmup-seconds", "0.05"], timeout=580)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -117,10 +117,10 @@ def test_two_rank_exchange_fields(gpu_ok):
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_one_gpu_line_carries_the_exchange(gpu_ok):
-    """The default command's N = 1 line carries namespace_exchange too (config D, partitioned,
+    """The --full command's N = 1 line carries namespace_exchange too (config D, partitioned,
     the headline's steps and warmup), so the driver's N = 1 run is the denominator of the
     exchange scaling ratio."""
-    p = run(["--frames", "65536", "--exchange-frames", "65536", "--steps", "6", "--warmup", "2", "--batches", "2",
+    p = run(["--full", "--frames", "65536", "--exchange-frames", "65536", "--steps", "6", "--warmup", "2", "--batches", "2",
              "--warmup-seconds", "0.05", "--no-cpu-baseline"], timeout=580)
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -129,6 +129,46 @@ def test_one_gpu_line_carries_the_exchange(gpu_ok):
     assert j["n_gpus"] == 1 and x["n_gpus"] == 1 and x["steps"] == 6 and x["value"] > 0
     assert x["exchange"]["mode"] == "partitioned" and x["exchange"]["one_stream_steps"]["value"] > 0
     assert "scaling_note" in j["config"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_dumps_the_last_steps_outputs(gpu_ok, oracle_built, tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline's line without the
+    measurements that take runs of their own; --dump-outputs writes the last timed step's
+    outputs as float arrays.  Step 2 + 5 - 1 of 2 batch slots reads slot 0, the workload as
+    synth makes it: records, queues and counters equal the oracle's on the same frames (20,000
+    frames of config C: every frame shape, 79 tiles, the last one partial)."""
+    import numpy as np
+    from emurx import abi, synth
+    from emurx.rx import hist_to_counters
+    n = 20000
+    p = run(["--gpus", "1", "--config", "C", "--frames", str(n), "--steps", "5", "--warmup", "2", "--batches", "2",
+             "--warmup-seconds", "0.05", "--dump-outputs", str(tmp_path)], timeout=280)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(p.stdout.splitlines()) == 1, p.stdout[-2000:]
+    j = json.loads(p.stdout)
+    assert j["steps"] == 5 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0
+    for k in ("roofline", "host_inclusive", "namespace_exchange", "cpu_baseline"):
+        assert k not in j, k
+    assert j["outputs_dumped"]["batch_slot"] == 0
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(got) == {"records", "record_rows", "queues", "queue_offsets", "histogram"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    w = synth.config_c(n, rank=0)
+    o = oracle_built.Oracle()
+    synth.load_tables(w, o)
+    orec, oq, oqoff, ocnt = o.rx_batch(w["buf"], w["desc"])
+    assert np.array_equal(got["record_rows"], np.arange(n))
+    want = np.stack([orec[k].astype(np.float64) for k in abi.REC_DTYPE.names], axis=1)
+    assert np.array_equal(got["records"], want)
+    assert np.array_equal(got["queues"], oq) and np.array_equal(got["queue_offsets"], oqoff)
+    hist = got["histogram"]
+    assert np.array_equal(hist, np.round(hist)) and hist[0::2].sum() == n  # one batch's share
+    cnt, ocnt = hist_to_counters(hist.astype(np.uint64)), oracle_built.counters_dict(ocnt)
+    for k in abi.PARSER_COUNTER_NAMES + ["ref_panic"]:
+        assert cnt[k] == ocnt[k], k
 
 
 @pytest.mark.gpu

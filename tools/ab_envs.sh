@@ -21,7 +21,7 @@ for cfg in $configs; do
       i=$((i + 1))
       [ "$e" = - ] && e="EMURX_AB_NONE=1"
       log=gpurun_out/ab/${cfg}_${i}_$r.log
-      env $e timeout -k 10 300 python bench.py $args --no-cpu-baseline --no-check > $log 2>&1 \
+      env $e timeout -k 10 300 python bench.py --full $args --no-cpu-baseline --no-check > $log 2>&1 \
         || { echo "fail $cfg [$e]"; tail -3 $log; exit 1; }
       echo "$cfg #$r [$e] $(tail -1 $log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; x=d.get("exchange") or {}; print(round(d["value"]), "one", r["kernel_ms_mean"], r["frac"], "pipe", r.get("pipelined",{}).get("interval_ms"), "step", d["ms_per_step"], ("xchg " + str(x.get("value"))) if x else "")')"
     done

@@ -12,10 +12,10 @@ for cfg in $configs; do
   args="--steps 30 --warmup 4"; [ $cfg != B ] && args="--config $cfg --steps 30 --warmup 4"
   for v in "$@"; do
     lib=$PWD/trex-emu_amd/lib/libemurx.so; [ $v != default ] && lib=$PWD/trex-emu_amd/lib/libemurx_$v.so
-    EMURX_LIB=$lib timeout -k 10 120 python bench.py $args --no-cpu-baseline --no-check --no-replay > $out/${cfg}_$v.log 2>&1 || { echo "fail $cfg $v"; tail -3 $out/${cfg}_$v.log; exit 1; }
+    EMURX_LIB=$lib timeout -k 10 120 python bench.py --full $args --no-cpu-baseline --no-check --no-replay > $out/${cfg}_$v.log 2>&1 || { echo "fail $cfg $v"; tail -3 $out/${cfg}_$v.log; exit 1; }
     t=$(tail -1 $out/${cfg}_$v.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["roofline"]["kernel_ms_mean"], d["roofline"]["pipelined"]["interval_ms"])')
     EMURX_LIB=$lib timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_BRANCH \
-      -T --kernel-include-regex k_rx -d $out/p_${cfg}_$v -o run --output-format csv -- python bench.py $args --no-cpu-baseline --no-check --no-replay > $out/p_${cfg}_$v.log 2>&1 || { echo "pmc fail $cfg $v"; tail -3 $out/p_${cfg}_$v.log; exit 1; }
+      -T --kernel-include-regex k_rx -d $out/p_${cfg}_$v -o run --output-format csv -- python bench.py --full $args --no-cpu-baseline --no-check --no-replay > $out/p_${cfg}_$v.log 2>&1 || { echo "pmc fail $cfg $v"; tail -3 $out/p_${cfg}_$v.log; exit 1; }
     c=$(python - "$out/p_${cfg}_$v" <<'PY'
 import csv, glob, sys, collections
 per = collections.defaultdict(float)

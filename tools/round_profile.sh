@@ -38,10 +38,10 @@ for ph in $phases; do
       bench)
         extra="--no-cpu-baseline"
         [ "$c" = B ] && extra="--host-path"
-        step bench_$c 600 python bench.py $(args $c) $extra ;;
+        step bench_$c 600 python bench.py --full $(args $c) $extra ;;
       prof)
         step prof_$c 300 rocprofv3 --kernel-trace --stats -d $out/prof_$c -o run --output-format csv \
-          -- python bench.py $(args $c) --no-cpu-baseline --no-exchange-run
+          -- python bench.py --full $(args $c) --no-cpu-baseline --no-exchange-run
         f=$(ls $out/prof_$c/*/run_kernel_stats.csv $out/prof_$c/run_kernel_stats.csv 2>/dev/null | head -n 1)
         [ -n "$f" ] && cut -d, -f1-4 "$f" | head -n 12
         t=$(ls $out/prof_$c/*/run_kernel_trace.csv $out/prof_$c/run_kernel_trace.csv 2>/dev/null | head -n 1)
@@ -52,7 +52,7 @@ for ph in $phases; do
       pmc)
         for k in FETCH_SIZE WRITE_SIZE; do
           step pmc_${c}_$k 180 rocprofv3 --pmc $k -T --kernel-include-regex k_rx -d $out/pmc_${c}/pmc_$k -o run \
-            --output-format csv -- python bench.py $(args $c) --steps 40 --warmup 8 --no-cpu-baseline --no-check --no-replay \
+            --output-format csv -- python bench.py --full $(args $c) --steps 40 --warmup 8 --no-cpu-baseline --no-check --no-replay \
             --no-exchange-run
         done
         xs=""  # E's excess is probe lines since the window-skip checksum (round 4); --excess-streamed before
