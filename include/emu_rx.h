@@ -562,6 +562,60 @@ int emurx_tx_checksum_dev(emurx_t* h, uint8_t* d_frames, const emurx_tx_desc* d_
 int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n,
                      uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off, uint64_t* d_info, void* stream);
 
+/* ---- the stateless answers on the device ------------------------------------------------
+   Three of the plugins' answers are a pure function of the frame and of a table the device
+   holds; emurx_respond_dev builds them from a classified batch, shaped for emurx_tx_zmq_dev:
+     ARP reply to a request for a client's IPv4   plugins/arp/arp.go:904-933 -> Respond :776-790
+     ICMPv4 echo reply                            plugins/icmp/icmp.go:396-461 -> HandleEcho :289-325
+     ICMPv6 echo reply                            plugins/ipv6/ipv6.go:465-504 -> HandleEcho :315-357
+   A frame is considered only if rec.status == EMURX_ST_OK, its lookup is EMURX_LK_CLIENT, its
+   callback is arp / icmp / icmpv6 and its descriptor is no hole; every other frame gets
+   EMURX_RSP_NONE.  d_rec: the records emurx_classify_dev wrote for d_frames / d_desc.
+     arp     the template's reply (14 + 4 per VLAN tag + 28 bytes, no padding): dst = the request's
+             sender hardware address, src = the client's MAC, one tag per non-zero rec.vlan[i]
+             (the Namespace key's TPID | VID), 0x0806, 00 01 08 00 06 04 00 02, {client MAC, the
+             request's target IP}, {the request's sender hardware address and IP}.  The MAC is
+             the IPv4 table slot's: the table is probed again with the record's tunnel key and
+             the target IP, and a probe that does not return rec.client_id (a partitioned handle
+             that does not own the Namespace, tables changed since the classify) gives
+             EMURX_RSP_HOST.
+     icmp    source IP neither loopback nor net.IP.IsGlobalUnicast (Go 1.18: 0.0.0.0,
+             255.255.255.255, 224.0.0.0/4, 169.254.0.0/16; Go's standard library, not the
+             reference tree) -> DROP_MCAST; then type, code (8, 0) -> reply, (13, 0) -> HOST, else
+             NONE; an Ethernet source with the group bit -> DROP_MCAST.  The reply is the whole
+             frame (tags and trailing bytes kept) with the Ethernet and the IPv4 addresses
+             swapped, type 0 and the checksum UpdateInetChecksum(cs, 0x0800, 0x0000).
+     icmpv6  an Ethernet source with the group bit -> DROP_MCAST; else the addresses swapped,
+             type 129, extension headers stripped (next header 58, payload length less
+             l4 - l3 - 40, p[l4:] moved down to l3 + 40, the frame shorter by as much), checksum
+             UpdateInetChecksum(cs, 0x8000, 0x8100).
+   Header offsets of a record that do not fit its frame (emurx_classify_dev writes none) give HOST.
+   Output: the replies compacted in rx frame order; reply k at d_out_desc[k].off, a multiple of
+   16 = the sum of align16(len) of the replies before it; d_out_desc[k] = {off, len, vport =
+   rec.vport, pad 0} (the array emurx_tx_zmq_dev takes); d_out_src[k] = the rx frame index.  The
+   up to 15 bytes between a reply's end and the next 16-byte boundary are unspecified; nothing is
+   written at or past out_cap, nor past the aligned end of the last reply; out_cap >=
+   sum(align16(desc.len)) always suffices.  d_info (u64[8]) = {replies written, bytes needed,
+   frames with outcome 1..6}.  With too small a buffer the replies that fit are written (a
+   prefix), the others get EMURX_RSP_NOSPC (so does a reply that would end past 4 GiB, the
+   descriptor's offset range) and d_info[1] tells the size needed.  d_out_desc and d_out_src
+   have capacity n; d_outcome [n] may be NULL.  d_out and d_rec 16-byte aligned, the descriptor
+   arrays 8-byte; frames are read as the aligned 16-byte blocks that hold them.  n <
+   EMURX_TX_ZMQ_MAX_FRAMES; n == 0 writes a zero d_info.  Three launches on `stream` (decide,
+   scan, emit), no host synchronisation, behind the table shipment emurx_classify_dev describes;
+   calls on different streams of one handle share its scratch, so they must not overlap. */
+enum emurx_rsp {            /* per-frame outcome, d_outcome[i] */
+    EMURX_RSP_NONE = 0,       /* not a frame this call answers */
+    EMURX_RSP_ARP = 1, EMURX_RSP_ICMP = 2, EMURX_RSP_ICMPV6 = 3,   /* reply written */
+    EMURX_RSP_DROP_MCAST = 4, /* the handler counts pktRxErrMulticastB and sends nothing */
+    EMURX_RSP_HOST = 5,       /* the Go handler must answer (timestamp request; client not in this handle's tables) */
+    EMURX_RSP_NOSPC = 6       /* a reply was due but did not fit out_cap */
+};
+int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                      const emurx_rec* d_rec, uint32_t n,
+                      uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
+                      uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
+
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);
 /* Sum the EMURX_HIST_SHARDS copies of a device histogram (after a D2H copy). */

@@ -48,6 +48,8 @@ GROUPS = [
      "(SURVEY §8e)"),
     ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev"],
      "gopacket checksum updates; `VethIFZmq.Send/FlushTx` `veth_zmq.go:149-200`"),
+    ("Device responder", ["emurx_respond_dev"],
+     "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

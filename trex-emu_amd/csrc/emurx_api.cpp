@@ -190,6 +190,8 @@ struct emurx_ctx {
     int txz_variant = EMURX_TXZ_WIDE, txz_mode = -1;
     uint32_t txz_calls = 0, txz_last_copy = 0, txz_every = 8, txz_same = 0;
     int last_txz = -1;
+    // the device responder's scratch (emurx_respond_dev): plans and tile sums, no state between calls
+    DevBuf<uint8_t> d_rsp;
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -869,6 +871,7 @@ void emurx_close(emurx_t* h) {
     h->d_nsinfo.release();
     for (auto& r : h->route) r.release();
     h->d_txz.release();
+    h->d_rsp.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
     for (auto& e : h->ev)
@@ -1367,6 +1370,30 @@ int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
         h->txz_last_copy = h->txz_calls;
     }
     return EMURX_OK;
+}
+
+int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                      uint32_t n, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t* d_out_src,
+                      uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    if (!h || !d_info || (n && (!d_frames || !d_desc || !d_rec || !d_out_desc || !d_out_src || (!d_out && out_cap))))
+        return EMURX_EINVAL;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_out & 15) || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) ||
+        ((uintptr_t)d_out_desc & 7) || ((uintptr_t)d_info & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // the ARP reply reads the IPv4 table: behind the shipment of pending edits, like a classify
+    if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
+    const size_t need = emurx_rsp_scratch_bytes(n);
+    if (need > h->d_rsp.n) {  // grows on demand; a launch in flight may still read the old one
+        (void)hipStreamSynchronize(st);
+        if (h->d_rsp.alloc(need)) return EMURX_ENOMEM;
+    }
+    return emurx_launch_respond(d_frames, d_desc, d_rec, n, h->tables(), d_out, out_cap, d_out_desc, d_out_src, d_outcome,
+                                d_info, h->d_rsp.p, st)
+               ? EMURX_EDEVICE
+               : EMURX_OK;
 }
 
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {

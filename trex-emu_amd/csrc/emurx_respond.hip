@@ -1,0 +1,474 @@
+// emurx_respond.hip — the three stateless answers on the device (gfx950): the ARP reply to a
+// request for a client's IPv4 (src/emu/plugins/arp/arp.go:904-933 -> Respond :776-790), the
+// ICMPv4 echo reply (plugins/icmp/icmp.go:396-461 -> HandleEcho :289-325) and the ICMPv6 echo
+// reply (plugins/ipv6/ipv6.go:465-504 -> HandleEcho :315-357).  emurx_respond_dev, three launches:
+//   k_rsp_decide   one frame per lane: the record (32 B) says whether the frame is a candidate
+//                  (status OK, lookup EMURX_LK_CLIENT, callback arp / icmp / icmpv6); only a
+//                  candidate's descriptor and a few header bytes are read (ARP: one probe of the
+//                  IPv4 table).  Outcome and reply length per frame; per 256-frame tile the
+//                  replies, their 16-byte rows and the DROP_MCAST / HOST counts.
+//   k_rsp_scan     one workgroup: exclusive scan of the tiles' replies and rows, d_info.
+//   k_rsp_emit     one workgroup per tile that has a reply: ordinals and byte offsets by a scan
+//                  of the tile's plans in LDS, the descriptors, then the tile's output rows dealt
+//                  over the 256 lanes (a 9216 B echo is 576 rows over 256 lanes, not one lane's
+//                  loop).  A reply row is one 16-byte span of the request (two aligned loads,
+//                  funnel-shifted; shifted by the stripped extension headers from l3 + 40 on),
+//                  patched in registers: the swapped Ethernet and IP addresses, which the frame's
+//                  own lane put into LDS once per reply, and at most six rewritten bytes (type,
+//                  checksum, payload length, next header).  The ARP reply (42-50 B, built from the
+//                  template) is written by its frame's own lane.
+// A batch without candidates costs the read of d_rec and one outcome byte per frame: the emit
+// workgroups of tiles without a reply leave after one 8-byte load.
+#include <hip/hip_runtime.h>
+
+#include "../../include/emu_rx.h"
+#include "emurx_kernels.h"
+#include "emurx_parse.h"
+
+namespace emurx {
+
+constexpr uint32_t kRspTile = EMURX_QUEUE_TILE;  // frames per workgroup, one per lane
+static_assert(kRspTile == kBlock, "one frame per lane of a 256-lane workgroup");
+constexpr uint32_t kRspScanBlock = 1024;
+
+// the plan of a frame (kept as outcome << 16 | reply length; a length is a descriptor's u16)
+struct RspPlan {
+    uint32_t outcome, len;
+};
+
+// UpdateInetChecksum (gopacket layers/icmp4.go:238-250): ~cs + ~old + new, folded, complemented
+__device__ __forceinline__ uint32_t rsp_update_csum(uint32_t cs, uint32_t oldv, uint32_t newv) {
+    uint32_t s = (~cs & 0xffffu) + (~oldv & 0xffffu) + newv;
+    while (s > 0xffffu) s = (s >> 16) + (s & 0xffffu);
+    return ~s & 0xffffu;
+}
+
+// Go 1.18 net.IP.IsLoopback || IsGlobalUnicast for an IPv4 address (bytes b0.b1.x.x, ip = the
+// four wire bytes little-endian): not 0.0.0.0, 255.255.255.255, 224.0.0.0/4, 169.254.0.0/16.
+// The rule is Go's standard library (net/ip.go), not the reference tree: as unpinned by the
+// reference's own tests as ip6_local_or_global (emurx_parse.h) is.
+__device__ __forceinline__ bool rsp_ip4_src_ok(uint32_t ip) {
+    const uint32_t b0 = ip & 0xff, b1 = (ip >> 8) & 0xff;
+    return !(ip == 0 || ip == 0xffffffffu || (b0 & 0xf0) == 0xe0 || (b0 == 169 && b1 == 254));
+}
+
+__device__ __forceinline__ uint32_t rsp_le32(const uint8_t* p) {  // any alignment
+    return gld1(p) | gld1(p + 1) << 8 | gld1(p + 2) << 16 | gld1(p + 3) << 24;
+}
+
+// the client of (record's tunnel key, ip) in the IPv4 table, with its MAC (CLookupByIPv4)
+__device__ __forceinline__ IpHit rsp_probe_ip4(const emurx_dev_tables& T, uint32_t ns, uint32_t vport, uint32_t v0,
+                                               uint32_t v1, uint32_t ip) {
+    const uint32_t b = emurx_ip4_hash(emurx_tk_hash(vport, v0, v1), ip) & T.ip4_mask;
+    return resolve_ip4(T, b, ld_bucket(T.ip4_tab, b), ns, ip);
+}
+
+// The record's words (emurx_rec): ns, client, vlan0, vlan1, vport | l3 << 16, l4 | l7 << 16,
+// l7_len | next_hdr << 16 | proto << 24, status | flags << 8 | rsv << 16
+__device__ __forceinline__ bool rsp_candidate(const uint4& b) {
+    const uint32_t proto = b.z >> 24, status = b.w & 0xff, lk = (b.w >> (8 + EMURX_FLAG_LK_SHIFT)) & 7u;
+    return status == EMURX_ST_OK && lk == EMURX_LK_CLIENT &&
+           (proto == EMURX_CB_ARP || proto == EMURX_CB_ICMP || proto == EMURX_CB_ICMPV6);
+}
+
+// The decision for a candidate frame.  Header offsets that do not fit the frame (no record of
+// emurx_classify_dev for these descriptors has them) give EMURX_RSP_HOST: never guess.
+__device__ RspPlan rsp_decide(const uint8_t* __restrict__ frames, const emurx_desc& d, const uint4& a, const uint4& b,
+                              const emurx_dev_tables& T) {
+    const uint32_t proto = b.z >> 24, l3 = b.x >> 16, l4 = b.y & 0xffffu, len = d.len;
+    const uint8_t* f = frames + d.off;
+    if (d.pad == EMURX_DESC_HOLE) return {EMURX_RSP_NONE, 0};
+    if (l3 < 14 || l3 > len) return {EMURX_RSP_HOST, 0};
+    if (proto == EMURX_CB_ARP) {
+        if (l3 + 28 > len) return {EMURX_RSP_HOST, 0};
+        const uint32_t tpa = rsp_le32(f + l3 + 24);
+        const IpHit h = rsp_probe_ip4(T, a.x, b.x & 0xffffu, a.z, a.w, tpa);
+        // a handle that does not hold the client (partitioned, or tables changed since the classify)
+        if (h.cid != a.y || h.cid == EMURX_ID_NONE) return {EMURX_RSP_HOST, 0};
+        return {EMURX_RSP_ARP, 42u + 4u * ((a.z != 0) + (a.w != 0))};
+    }
+    const bool group_src = gld1(f + 6) & 1;  // broadcast or group bit: eth.IsBroadcast() || IsMcast() after the swap
+    if (proto == EMURX_CB_ICMP) {
+        if (l3 + 20 > len || l4 + 8 > len) return {EMURX_RSP_HOST, 0};
+        if (!rsp_ip4_src_ok(rsp_le32(f + l3 + 12))) return {EMURX_RSP_DROP_MCAST, 0};  // icmp.go:429-436
+        const uint32_t tc = gld1(f + l4) << 8 | gld1(f + l4 + 1);
+        if (tc == 0x0d00u) return {EMURX_RSP_HOST, 0};  // timestamp request: wall-clock time
+        if (tc != 0x0800u) return {EMURX_RSP_NONE, 0};
+        if (group_src) return {EMURX_RSP_DROP_MCAST, 0};
+        return {EMURX_RSP_ICMP, len};
+    }
+    // ICMPv6 echo request (EMURX_LK_CLIENT implies type 128, code 0)
+    if (l3 + 40 > l4 || l4 + 8 > len) return {EMURX_RSP_HOST, 0};
+    if (group_src) return {EMURX_RSP_DROP_MCAST, 0};
+    // the extension headers go (ipv6.go:331-345); a next header that disagrees with l4 is no parse of ours
+    const uint32_t strip = l4 - l3 - 40;
+    if ((gld1(f + l3 + 6) != 58) != (strip != 0)) return {EMURX_RSP_HOST, 0};
+    return {EMURX_RSP_ICMPV6, len - strip};
+}
+
+// tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows
+__global__ __launch_bounds__(kBlock) void k_rsp_decide(const uint8_t* __restrict__ frames,
+                                                       const emurx_desc* __restrict__ desc,
+                                                       const emurx_rec* __restrict__ rec, uint32_t n,
+                                                       const emurx_dev_tables T, uint32_t* __restrict__ plan,
+                                                       uint2* __restrict__ tsum, uint8_t* __restrict__ outcome) {
+    __shared__ uint32_t s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kRspTile + threadIdx.x;
+    RspPlan p{EMURX_RSP_NONE, 0};
+    if (i < n) {
+        const uint4 b = gld16(reinterpret_cast<const uint4*>(rec + i) + 1);
+        if (rsp_candidate(b)) {
+            const uint4 a = gld16(reinterpret_cast<const uint4*>(rec + i));
+            p = rsp_decide(frames, desc[i], a, b, T);
+        }
+        if (outcome) outcome[i] = (uint8_t)p.outcome;
+    }
+    const bool reply = p.outcome >= EMURX_RSP_ARP && p.outcome <= EMURX_RSP_ICMPV6;
+    const uint32_t c = wave_sum_u32((reply ? 1u : 0u) | (p.outcome == EMURX_RSP_DROP_MCAST ? 1u << 10 : 0u) |
+                                    (p.outcome == EMURX_RSP_HOST ? 1u << 20 : 0u));
+    const uint32_t r = wave_sum_u32(reply ? (p.len + 15) >> 4 : 0u);
+    if (lane_id() == 0 && (c | r)) {
+        atomicAdd(&s_sum[0], c);
+        atomicAdd(&s_sum[1], r);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) tsum[blockIdx.x] = make_uint2(s_sum[0], s_sum[1]);
+    // the plans are read by the emit pass of tiles that have a reply only
+    if ((s_sum[0] & 0x3ffu) && i < n) plan[i] = p.outcome << 16 | p.len;
+}
+
+// inclusive scan over a workgroup of kRspScanBlock lanes (s_w: one word pair per wave)
+__device__ __forceinline__ void rsp_block_scan(uint32_t& c, unsigned long long& r, uint32_t (*s_c)[2],
+                                               unsigned long long* s_r) {
+    const uint32_t lane = lane_id(), wv = threadIdx.x / kWave, nw = blockDim.x / kWave;
+#pragma unroll
+    for (uint32_t d = 1; d < kWave; d <<= 1) {
+        const uint32_t uc = (uint32_t)__shfl_up((int)c, d);
+        const unsigned long long ur = __shfl_up(r, d);
+        if (lane >= d) {
+            c += uc;
+            r += ur;
+        }
+    }
+    __syncthreads();  // the previous round's readers
+    if (lane == kWave - 1) {
+        s_c[wv][0] = c;
+        s_r[wv] = r;
+    }
+    __syncthreads();
+    for (uint32_t w = 0; w < nw; ++w) {
+        if (w < wv) {
+            c += s_c[w][0];
+            r += s_r[w];
+        }
+    }
+}
+
+// info: {n_out, bytes needed, count of outcomes 1..6}: the scan writes bytes needed, DROP_MCAST
+// and HOST and zeroes the rest; the emit pass adds n_out, the replies by kind and NOSPC
+__global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restrict__ tsum, uint32_t ntiles,
+                                                            uint32_t* __restrict__ tord,
+                                                            unsigned long long* __restrict__ trow,
+                                                            unsigned long long* __restrict__ info) {
+    __shared__ uint32_t s_c[kRspScanBlock / kWave][2];
+    __shared__ unsigned long long s_r[kRspScanBlock / kWave];
+    __shared__ uint32_t s_dh[2];
+    if (threadIdx.x < 2) s_dh[threadIdx.x] = 0;
+    uint32_t cbase = 0, drop = 0, host = 0;
+    unsigned long long rbase = 0;
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += kRspScanBlock) {  // workgroup-uniform trip count
+        const uint32_t t = t0 + threadIdx.x;
+        const uint2 v = t < ntiles ? tsum[t] : make_uint2(0, 0);
+        const uint32_t cnt = v.x & 0x3ffu;
+        drop += (v.x >> 10) & 0x3ffu;
+        host += v.x >> 20;
+        uint32_t c = cnt;
+        unsigned long long r = v.y;
+        rsp_block_scan(c, r, s_c, s_r);
+        if (t < ntiles) {
+            tord[t] = cbase + c - cnt;
+            trow[t] = rbase + r - v.y;
+        }
+        __syncthreads();
+        if (threadIdx.x == kRspScanBlock - 1) {
+            s_c[0][1] = c;
+            s_r[0] = r;
+        }
+        __syncthreads();
+        cbase += s_c[0][1];
+        rbase += s_r[0];
+    }
+    drop = wave_sum_u32(drop);
+    host = wave_sum_u32(host);
+    __syncthreads();
+    if (lane_id() == 0) {
+        atomicAdd(&s_dh[0], drop);
+        atomicAdd(&s_dh[1], host);
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const uint32_t k = threadIdx.x;
+        info[k] = k == 1 ? rbase * 16ull : k == 2 + EMURX_RSP_DROP_MCAST - 1 ? s_dh[0] : k == 2 + EMURX_RSP_HOST - 1 ? s_dh[1] : 0ull;
+    }
+}
+
+// E[s .. s + 16) of the frame E = [F, F + flen), s of either sign, as four little-endian words:
+// the two aligned 16-byte blocks that hold the span, read only where they hold a byte of the
+// frame (zeros elsewhere: the caller masks those bytes out), funnel-shifted
+__device__ __forceinline__ void rsp_load16(uintptr_t F, uint32_t flen, int s, uint32_t o[4]) {
+    const uintptr_t a = F + (intptr_t)s, A = a & ~(uintptr_t)15, Fend = F + flen;
+    const uint32_t sh = (uint32_t)(a & 15), q = sh >> 2, bsh = sh & 3;
+    uint4 x = make_uint4(0, 0, 0, 0), y = x;
+    if (A < Fend && A + 16 > F) x = gld16(reinterpret_cast<const void*>(A));
+    if (sh && A + 16 < Fend && A + 32 > F) y = gld16(reinterpret_cast<const void*>(A + 16));
+    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t lo = q == 0 ? w[i] : q == 1 ? w[i + 1] : q == 2 ? w[i + 2] : w[i + 3];
+        const uint32_t hi = q == 0 ? w[i + 1] : q == 1 ? w[i + 2] : q == 2 ? w[i + 3] : w[i + 4];
+        o[i] = __builtin_amdgcn_alignbyte(hi, lo, bsh);
+    }
+}
+// the mask of the bytes [lo, hi) of a row (0 <= lo < hi <= 16) that lie in its dword d
+__device__ __forceinline__ uint32_t rsp_bytes(int lo, int hi, int d) {
+    const int a = max(lo - 4 * d, 0), b = min(hi - 4 * d, 4);
+    if (a >= b) return 0;
+    return (b == 4 ? 0xffffffffu : (1u << (8 * b)) - 1u) & ~((1u << (8 * a)) - 1u);
+}
+// byte `pos` of the reply, if it lies in the row that starts at y0, becomes v
+__device__ __forceinline__ void rsp_set_byte(uint32_t o[4], uint32_t y0, uint32_t pos, uint32_t v) {
+    const uint32_t j = pos - y0;
+    if (j >= 16) return;
+    // selects on the four words, not a store at a computed index (which would put the row in scratch)
+    const uint32_t sh = 8 * (j & 3), w = j >> 2, m = ~(0xffu << sh), x = v << sh;
+    o[0] = w == 0 ? (o[0] & m) | x : o[0];
+    o[1] = w == 1 ? (o[1] & m) | x : o[1];
+    o[2] = w == 2 ? (o[2] & m) | x : o[2];
+    o[3] = w == 3 ? (o[3] & m) | x : o[3];
+}
+
+// what the rows' lanes need of a reply, per reply of the tile
+struct RspReply {
+    uint32_t src;    // the request's offset in the frame buffer
+    uint32_t lens;   // request length | kind (EMURX_RSP_*, 0: do not write) << 16
+    uint32_t l3l4;   // l3 | the request's l4 << 16
+    uint32_t cs;     // the new checksum | the new IPv6 payload length << 16
+};
+
+__global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__ frames,
+                                                     const emurx_desc* __restrict__ desc,
+                                                     const emurx_rec* __restrict__ rec, uint32_t n,
+                                                     const emurx_dev_tables T, const uint32_t* __restrict__ plan,
+                                                     const uint2* __restrict__ tsum, const uint32_t* __restrict__ tord,
+                                                     const unsigned long long* __restrict__ trow,
+                                                     uint8_t* __restrict__ out, unsigned long long cap,
+                                                     emurx_desc* __restrict__ odesc, uint32_t* __restrict__ osrc,
+                                                     uint8_t* __restrict__ outcome, unsigned long long* __restrict__ info) {
+    __shared__ uint32_t s_w[kWaves][2];
+    __shared__ uint32_t s_row[kRspTile + 1];  // first row (in the tile) of reply k; [replies] = the tile's rows
+    __shared__ RspReply s_rep[kRspTile];
+    __shared__ uint32_t s_mac[kRspTile][3];   // an echo reply's first 12 bytes: the Ethernet addresses swapped
+    __shared__ uint32_t s_ip[kRspTile][10];   // its IP addresses swapped (8 or 32 bytes) between two pad dwords
+    __shared__ uint32_t s_cnt[5];             // written replies by kind (1..3), NOSPC
+    const uint32_t t = blockIdx.x;
+    const uint2 ts = tsum[t];
+    const uint32_t replies = ts.x & 0x3ffu;
+    if (!replies) return;  // workgroup-uniform
+    const uint32_t lane = lane_id(), wv = threadIdx.x / kWave, i = t * kRspTile + threadIdx.x;
+    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
+    const uint32_t ord0 = tord[t];
+    const unsigned long long row0 = trow[t];
+    const uint32_t p = i < n ? plan[i] : 0u;
+    const uint32_t kind = p >> 16, rlen = p & 0xffffu;
+    const bool reply = kind >= EMURX_RSP_ARP && kind <= EMURX_RSP_ICMPV6;
+    const uint32_t rows = reply ? (rlen + 15) >> 4 : 0u;
+    // ordinal and first row inside the tile: wave scans, then the waves' totals
+    uint32_t k = reply ? 1u : 0u, r = rows;
+#pragma unroll
+    for (uint32_t d = 1; d < kWave; d <<= 1) {
+        const uint32_t uk = (uint32_t)__shfl_up((int)k, d), ur = (uint32_t)__shfl_up((int)r, d);
+        if (lane >= d) {
+            k += uk;
+            r += ur;
+        }
+    }
+    if (lane == kWave - 1) {
+        s_w[wv][0] = k;
+        s_w[wv][1] = r;
+    }
+    __syncthreads();
+    for (uint32_t w = 0; w < wv; ++w) {
+        k += s_w[w][0];
+        r += s_w[w][1];
+    }
+    k -= reply ? 1u : 0u;
+    r -= rows;
+    if (threadIdx.x == 0) s_row[replies] = ts.y;
+    // the reply's place: EMURX_RSP_NOSPC when it does not fit out_cap (or emurx_desc's 32-bit
+    // offset); offsets ascend, so the replies that fit are a prefix and keep their ordinals
+    const unsigned long long off = (row0 + r) * 16ull, end = off + 16ull * rows;
+    const bool fits = end <= cap && end <= (1ull << 32);
+    if (reply) {
+        const uint4 a = gld16(reinterpret_cast<const uint4*>(rec + i));
+        const uint4 b = gld16(reinterpret_cast<const uint4*>(rec + i) + 1);
+        const emurx_desc d = desc[i];
+        const uint32_t l3 = b.x >> 16, l4 = b.y & 0xffffu, vport = b.x & 0xffffu;
+        const uint8_t* f = frames + d.off;
+        RspReply e{d.off, (uint32_t)d.len, l3 | l4 << 16, 0};
+        if (fits) {
+            odesc[ord0 + k] = emurx_desc{(uint32_t)off, (uint16_t)rlen, (uint8_t)vport, 0};
+            osrc[ord0 + k] = i;
+            if (kind == EMURX_RSP_ARP) {
+                // the template's reply (arp.go:621-636,776-790, ns_ctx.go:634-653): the frame's own
+                // lane writes its 3 or 4 rows.  The client's MAC is the IPv4 slot's (the probe of
+                // k_rsp_decide again; a miss now cannot happen on one stream: the reply is still
+                // the decided length, with a zero MAC)
+                const uint32_t tpa = rsp_le32(f + l3 + 24);
+                const IpHit h = rsp_probe_ip4(T, a.x, vport, a.z, a.w, tpa);
+                const uint32_t m03 = h.cid == a.y ? h.mlo : 0u, m45 = h.cid == a.y ? h.mhip & 0xffffu : 0u;
+                const uint32_t s03 = rsp_le32(f + l3 + 8), s45 = gld1(f + l3 + 12) | gld1(f + l3 + 13) << 8;
+                const uint32_t spa = rsp_le32(f + l3 + 14);
+                const uint32_t ntag = (a.z != 0) + (a.w != 0);
+                const uint32_t tag0 = __builtin_bswap32(a.z ? a.z : a.w), tag1 = __builtin_bswap32(a.w);
+                // dst = the request's sender hardware address, src = the client; then, from the
+                // EtherType on: 0806 0001 0800 06 04 0002, client MAC, target IP, sender MAC, sender IP
+                const uint32_t head[3] = {s03, s45 | m03 << 16, m03 >> 16 | m45 << 16};
+                const uint32_t body[8] = {0x01000608u, 0x04060008u, 0x00000200u | m03 << 16, m03 >> 16 | m45 << 16,
+                                          tpa, s03, s45 | spa << 16, spa >> 16};
+                uint32_t w[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const uint32_t w0 = j < 3 ? head[j] : j < 11 ? body[j - 3] : 0u;
+                    const uint32_t w1 = j < 3 ? head[j] : j == 3 ? tag0 : j < 12 ? body[j - 4] : 0u;
+                    const uint32_t w2 = j < 3 ? head[j] : j == 3 ? tag0 : j == 4 ? tag1 : j < 13 ? body[j - 5] : 0u;
+                    w[j] = ntag == 0 ? w0 : ntag == 1 ? w1 : w2;
+                }
+                uint4* o = reinterpret_cast<uint4*>(out + off);
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j)
+                    if (j < rows) o[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+            } else {
+                const uint32_t l4n = kind == EMURX_RSP_ICMP ? l4 : l3 + 40;  // the reply's l4
+                const uint32_t ocs = gld1(f + l4 + 2) << 8 | gld1(f + l4 + 3);
+                const uint32_t ncs = kind == EMURX_RSP_ICMP ? rsp_update_csum(ocs, 0x0800u, 0x0000u)
+                                                            : rsp_update_csum(ocs, 0x8000u, 0x8100u);
+                uint32_t plen = 0;
+                if (kind == EMURX_RSP_ICMPV6)  // PayloadLength() - optionbytes, uint16 (ipv6.go:335)
+                    plen = ((gld1(f + l3 + 4) << 8 | gld1(f + l3 + 5)) - (l4 - l4n)) & 0xffffu;
+                e.cs = ncs | plen << 16;
+                e.lens |= kind << 16;
+                // the swapped addresses, once per reply: Ethernet (row 0's first 12 bytes) and IP
+                const uintptr_t Fa = (uintptr_t)f;
+                uint32_t m[4], s[4], t[4] = {0, 0, 0, 0};
+                rsp_load16(Fa, d.len, 0, m);
+                s_mac[k][0] = m[1] >> 16 | m[2] << 16;
+                s_mac[k][1] = m[2] >> 16 | m[0] << 16;
+                s_mac[k][2] = m[0] >> 16 | m[1] << 16;
+                const bool v6 = kind == EMURX_RSP_ICMPV6;
+                rsp_load16(Fa, d.len, (int)(l3 + (v6 ? 8u : 12u)), s);  // IPv4: source, destination in s[0], s[1]
+                if (v6) rsp_load16(Fa, d.len, (int)(l3 + 24), t);
+                s_ip[k][0] = 0;  // the pad ahead: a dword that begins before the addresses
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s_ip[k][1 + j] = v6 ? t[j] : j == 0 ? s[1] : j == 1 ? s[0] : 0u;
+                    s_ip[k][5 + j] = v6 ? s[j] : 0u;
+                }
+                s_ip[k][9] = 0;
+            }
+        } else if (outcome) {
+            outcome[i] = EMURX_RSP_NOSPC;
+        }
+        s_row[k] = r;
+        s_rep[k] = e;
+        atomicAdd(&s_cnt[fits ? kind : 4u], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {  // info[1 + outcome] counts the outcome; info[0] = the replies written
+        const uint32_t j = threadIdx.x;
+        const uint32_t c = j ? s_cnt[j] : s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (c) atomicAdd(&info[j == 0 ? 0u : j == 4 ? 1u + EMURX_RSP_NOSPC : 1u + j], (unsigned long long)c);
+    }
+    // ---- the echo replies' rows, dealt over the lanes
+    const uint32_t R = ts.y;
+    for (uint32_t x = threadIdx.x; x < R; x += kBlock) {
+        uint32_t lo = 0, hi = replies;  // the reply whose rows hold x: the last k with s_row[k] <= x
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_row[mid] <= x) lo = mid;
+            else hi = mid;
+        }
+        const RspReply e = s_rep[lo];
+        const uint32_t ek = e.lens >> 16;
+        if (ek != EMURX_RSP_ICMP && ek != EMURX_RSP_ICMPV6) continue;  // ARP, or no room
+        const bool v6 = ek == EMURX_RSP_ICMPV6;
+        const uint32_t flen = e.lens & 0xffffu, l3 = e.l3l4 & 0xffffu, l4 = e.l3l4 >> 16;
+        const uint32_t strip = v6 ? l4 - l3 - 40 : 0u;
+        const uint32_t y0 = 16 * (x - s_row[lo]);
+        // One shifted 16-byte span of the request per row: reply[y] = E[y], or E[y + strip] from
+        // l3 + 40 on (IPv6: p[l4:] moved down).  A row that straddles l3 + 40 takes the shifted
+        // span: its bytes below l3 + 40 are all address bytes (32 of them end there), which
+        // come from the swapped copy in LDS like the Ethernet addresses of row 0.
+        const uintptr_t F = (uintptr_t)(frames + e.src);
+        uint32_t o[4];
+        rsp_load16(F, flen, (int)(y0 + (v6 && y0 + 16 > l3 + 40 ? strip : 0u)), o);
+        if (y0 == 0) {
+            o[0] = s_mac[lo][0];
+            o[1] = s_mac[lo][1];
+            o[2] = s_mac[lo][2];
+        }
+        const uint32_t astart = l3 + (v6 ? 8u : 12u), aend = astart + (v6 ? 32u : 8u);
+        if (y0 + 16 > astart && y0 < aend) {
+#pragma unroll
+            for (int dw = 0; dw < 4; ++dw) {
+                const int a = (int)astart - (int)(y0 + 4 * dw), b = (int)aend - (int)(y0 + 4 * dw);  // in this dword
+                if (a < 4 && b > 0) {
+                    const uint32_t q = (uint32_t)(4 - a);  // s_ip byte of the dword's first byte (one pad dword ahead)
+                    const uint32_t v = __builtin_amdgcn_alignbyte(s_ip[lo][(q >> 2) + 1], s_ip[lo][q >> 2], q & 3);
+                    const uint32_t m = rsp_bytes(a, b, 0);
+                    o[dw] = (o[dw] & ~m) | (v & m);
+                }
+            }
+        }
+        const uint32_t tpos = v6 ? l3 + 40 : l4;
+        rsp_set_byte(o, y0, tpos, v6 ? 129u : 0u);
+        rsp_set_byte(o, y0, tpos + 2, (e.cs >> 8) & 0xff);
+        rsp_set_byte(o, y0, tpos + 3, e.cs & 0xff);
+        if (strip) {
+            rsp_set_byte(o, y0, l3 + 4, e.cs >> 24);
+            rsp_set_byte(o, y0, l3 + 5, (e.cs >> 16) & 0xff);
+            rsp_set_byte(o, y0, l3 + 6, 58u);
+        }
+        *reinterpret_cast<uint4*>(out + (row0 + x) * 16ull) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+}  // namespace emurx
+
+// scratch: plan u32 [n], tile sums uint2 [ntiles], tile ordinals u32 [ntiles], tile rows u64 [ntiles]
+static size_t rsp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+size_t emurx_rsp_scratch_bytes(uint32_t n) {
+    const size_t nt = (n + emurx::kRspTile - 1) / emurx::kRspTile;
+    return rsp_align((size_t)n * 4) + rsp_align(nt * 8) + rsp_align(nt * 4) + rsp_align(nt * 8);
+}
+
+int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
+                         const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc, uint32_t* out_src,
+                         uint8_t* outcome, uint64_t* info, void* scratch, hipStream_t st) {
+    using namespace emurx;
+    unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
+    if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 64, st)) ? 0 : -1;
+    const uint32_t nt = (n + kRspTile - 1) / kRspTile;
+    uint8_t* p = static_cast<uint8_t*>(scratch);
+    uint32_t* plan = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)n * 4);
+    uint2* tsum = reinterpret_cast<uint2*>(p); p += rsp_align((size_t)nt * 8);
+    uint32_t* tord = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)nt * 4);
+    unsigned long long* trow = reinterpret_cast<unsigned long long*>(p);
+    hipError_t e = emurx_launch(k_rsp_decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, plan, tsum, outcome);
+    if (e == hipSuccess) e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, tsum, nt, tord, trow, inf);
+    if (e == hipSuccess)
+        e = emurx_launch(k_rsp_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, plan, tsum, tord, trow, out,
+                         (unsigned long long)cap, out_desc, out_src, outcome, inf);
+    return EMURX_HIP_OK(e) ? 0 : -1;
+}

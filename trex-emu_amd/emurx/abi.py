@@ -110,6 +110,9 @@ TX_IPV4_HDR, TX_V6_NH, TX_L4_SHIFT = 0x01, 0x02, 4
 TX_L4_NONE, TX_L4_TCP4, TX_L4_UDP4, TX_L4_TCP6, TX_L4_UDP6, TX_L4_ICMP6, TX_L4_ICMP4 = range(7)
 TX_OK, TX_RANGE = 0, 1
 ZMQ_TX_BURST, ZMQ_TX_MAX_BUFFER, ZMQ_PKT_MAGIC = 64, 32768, 0xAA  # veth_zmq.go:36-37, :167
+TX_ZMQ_MAX_FRAMES = 1 << 26  # EMURX_TX_ZMQ_MAX_FRAMES: n of tx_zmq_dev / respond_dev is below it
+# enum emurx_rsp: the per-frame outcome of emurx_respond_dev
+RSP_NONE, RSP_ARP, RSP_ICMP, RSP_ICMPV6, RSP_DROP_MCAST, RSP_HOST, RSP_NOSPC = range(7)
 FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xFFFFFFF0, 0xFFFFFFF1,
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
@@ -220,6 +223,7 @@ SIGNATURES = [
     ("emurx_ingest_stream", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("emurx_tx_checksum_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
+    ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -269,7 +273,7 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
-           "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+           "emurx_respond.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_parse.h", "emurx_mirror.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()
