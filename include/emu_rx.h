@@ -609,12 +609,64 @@ enum emurx_rsp {            /* per-frame outcome, d_outcome[i] */
     EMURX_RSP_ARP = 1, EMURX_RSP_ICMP = 2, EMURX_RSP_ICMPV6 = 3,   /* reply written */
     EMURX_RSP_DROP_MCAST = 4, /* the handler counts pktRxErrMulticastB and sends nothing */
     EMURX_RSP_HOST = 5,       /* the Go handler must answer (timestamp request; client not in this handle's tables) */
-    EMURX_RSP_NOSPC = 6       /* a reply was due but did not fit out_cap */
+    EMURX_RSP_NOSPC = 6,      /* a reply was due but did not fit out_cap */
+    EMURX_RSP_ND = 7          /* reply written (neighbour advertisement; emurx_respond_kinds_dev only) */
 };
 int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
                       const emurx_rec* d_rec, uint32_t n,
                       uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
                       uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
+/* The same call with the answers chosen by `kinds`, and a fourth answer, ARP's IPv6 counterpart:
+     neighbour advertisement (NA) to a neighbour solicitation (NS)
+                                   plugins/ipv6/nd.go:1546-1685 -> NdClientCtx.Respond :1220-1253
+   kinds == 0 or a bit above EMURX_RSPK_ALL is EMURX_EINVAL; a frame of a kind that was not
+   selected gets EMURX_RSP_NONE.  d_info is u64[EMURX_RSP_INFO_WORDS] = {replies written, bytes
+   needed, frames with outcome 1..7, zeros}.  Everything else is emurx_respond_dev's contract,
+   which is this call with kinds = ARP | ICMP | ICMPV6 and the eight-word d_info.
+     nd      considered only if rec.status == EMURX_ST_OK, the callback is icmpv6, the lookup is
+             EMURX_LK_NS_LEVEL, the descriptor is no hole and p[l4], p[l4+1] == 135, 0.  The device
+             writes a reply if and only if the Go handler would reach nd.Respond; where it cannot
+             cheaply decide it gives HOST, and NONE / HOST leave the Go handler running as today.
+             Header offsets that do not fit the frame (l3 < 14, l3 + 40 > l4, l4 + 4 > len; checked
+             before the type byte is read) -> HOST.  len - (l4 + 4) < 20 -> NONE (nd.go:1550-1553).
+             The options are p[l4+24 : len], the rest of the frame and not the IPv6 payload length
+             (gopacket layers/icmp6msg.go:299-312, 497-529): none -> no source link-layer address
+             (SLLA); 8 bytes -> the SLLA if {type 1, length 1}, else NONE (a wrong option, a zero
+             length and a truncated option are all errors, nd.go:1555-1587); 1..7 bytes -> NONE;
+             more than 8 -> HOST (a lane walks no option chain).  Then, each NONE (nd.go:1561-1609):
+             hop limit p[l3+7] != 255; an all-zero SLLA; source unspecified with an SLLA; source
+             unspecified and destination not multicast; target unspecified or multicast.  NdLearn
+             (:1611-1620) stays on the host and does not change the answer.  The target must be
+             net.IP.IsLinkLocalUnicast or IsGlobalUnicast (else NONE, :1622-1624).  An EUI-64
+             target (t[11], t[12] == ff, fe; ExtractOnlyMac core/client_ctx.go:314-329): the MAC
+             table is probed with the record's tunnel key and the extracted MAC (a zero MAC never
+             matches); miss -> NONE; IsValidPrefix (core/client_ctx.go:279-295: t[0:8] is fe80::/64
+             or the client's RA prefix of length 64) else NONE; a client without the ipv6 plugin ->
+             NONE; else the reply carries that MAC (:1626-1652).  Any other target: not global ->
+             NONE; CLookupByIPv6 in the IPv6 table, miss -> NONE, no ipv6 plugin -> NONE, else the
+             reply carries the slot's client MAC (:1653-1678).  The net.IP predicates are Go
+             1.18's on a 16-byte slice, IPv4-mapped readings included (::ffff:0.0.0.0 is
+             unspecified, ::ffff:224.x multicast, ::ffff:169.254.x link-local): Go's standard
+             library, not the reference tree, pinned by no capture.
+             The reply (nd.go:835-865, 1220-1253) is 14 + 4 per non-zero rec.vlan[i] + 72 bytes:
+             Ethernet source the client MAC, the tags as in the ARP reply, 86dd; 60 00 00 00 00 20
+             3a ff; 88 00 cs cs fl 00 00 00, the target, 02 01, the client MAC.  Source specified:
+             Ethernet destination the request's p[6:12], IPv6 source the target, IPv6 destination
+             the request's source, fl = 0x60.  Source unspecified (duplicate address detection):
+             Ethernet destination 33:33:00:00:00:01, IPv6 source the client's link-local address
+             fe80::(mac[0]^2) mac[1] mac[2] ff fe mac[3..5], IPv6 destination ff02::1, fl = 0.  cs
+             is the ICMPv6 checksum over the pseudo header (length 32, next header 58) and the 32
+             bytes (FixIcmpL4Checksum, gopacket layers/ip6.go:54-56). */
+#define EMURX_RSPK_ARP 1u
+#define EMURX_RSPK_ICMP 2u
+#define EMURX_RSPK_ICMPV6 4u
+#define EMURX_RSPK_ND 8u            /* neighbour solicitation -> neighbour advertisement */
+#define EMURX_RSPK_ALL 15u
+#define EMURX_RSP_INFO_WORDS 16
+int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                            const emurx_rec* d_rec, uint32_t n, uint32_t kinds,
+                            uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
+                            uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
 
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);

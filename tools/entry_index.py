@@ -48,8 +48,9 @@ GROUPS = [
      "(SURVEY §8e)"),
     ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev"],
      "gopacket checksum updates; `VethIFZmq.Send/FlushTx` `veth_zmq.go:149-200`"),
-    ("Device responder", ["emurx_respond_dev"],
-     "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`"),
+    ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev"],
+     "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`, "
+     "`NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

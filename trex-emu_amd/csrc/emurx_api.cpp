@@ -1372,28 +1372,46 @@ int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
     return EMURX_OK;
 }
 
-int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
-                      uint32_t n, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t* d_out_src,
-                      uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+// emurx_respond_dev and emurx_respond_kinds_dev: one implementation, the answers chosen by `kinds`
+// and the words of d_info that are written by `info_words`
+static int respond_kinds(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                         uint32_t n, uint32_t kinds, uint32_t info_words, uint8_t* d_out, uint64_t out_cap,
+                         emurx_desc* d_out_desc, uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
     if (!h || !d_info || (n && (!d_frames || !d_desc || !d_rec || !d_out_desc || !d_out_src || (!d_out && out_cap))))
         return EMURX_EINVAL;
+    if (kinds == 0 || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
     if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_out & 15) || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) ||
         ((uintptr_t)d_out_desc & 7) || ((uintptr_t)d_info & 7))
         return EMURX_EINVAL;
     int rc = bind(h);
     if (rc) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    // the ARP reply reads the IPv4 table: behind the shipment of pending edits, like a classify
+    // the ARP reply reads the IPv4 table, the neighbour advertisement the MAC, IPv6 and client-info
+    // tables: behind the shipment of pending edits, like a classify
     if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
     const size_t need = emurx_rsp_scratch_bytes(n);
     if (need > h->d_rsp.n) {  // grows on demand; a launch in flight may still read the old one
         (void)hipStreamSynchronize(st);
         if (h->d_rsp.alloc(need)) return EMURX_ENOMEM;
     }
-    return emurx_launch_respond(d_frames, d_desc, d_rec, n, h->tables(), d_out, out_cap, d_out_desc, d_out_src, d_outcome,
-                                d_info, h->d_rsp.p, st)
+    return emurx_launch_respond(d_frames, d_desc, d_rec, n, kinds, h->tables(), d_out, out_cap, d_out_desc, d_out_src,
+                                d_outcome, d_info, info_words, h->d_rsp.p, st)
                ? EMURX_EDEVICE
                : EMURX_OK;
+}
+
+int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                      uint32_t n, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t* d_out_src,
+                      uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    return respond_kinds(h, d_frames, d_desc, d_rec, n, EMURX_RSPK_ARP | EMURX_RSPK_ICMP | EMURX_RSPK_ICMPV6, 8, d_out,
+                         out_cap, d_out_desc, d_out_src, d_outcome, d_info, stream);
+}
+
+int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                            uint32_t n, uint32_t kinds, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
+                            uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    return respond_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSP_INFO_WORDS, d_out, out_cap, d_out_desc, d_out_src,
+                         d_outcome, d_info, stream);
 }
 
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {

@@ -144,12 +144,14 @@ void emurx_comm_free(emurx_comm_state* c);   // emurx_comm.cpp: destroy a commun
 int emurx_launch_tx_csum(uint8_t* frames, const emurx_tx_desc* desc, uint32_t n, uint8_t* status,
                          hipStream_t st);
 
-// The device responder (emurx_respond.hip): see emurx_respond_dev.  scratch:
-// emurx_rsp_scratch_bytes(n), no initial state.  Three launches.
+// The device responder (emurx_respond.hip): see emurx_respond_dev / emurx_respond_kinds_dev.
+// kinds: EMURX_RSPK_*; info_words: 8 or EMURX_RSP_INFO_WORDS, the words of `info` that are written.
+// scratch: emurx_rsp_scratch_bytes(n), no initial state.  Three launches.
 size_t emurx_rsp_scratch_bytes(uint32_t n);
 int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
-                         const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc, uint32_t* out_src,
-                         uint8_t* outcome, uint64_t* info, void* scratch, hipStream_t st);
+                         uint32_t kinds, const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc,
+                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, void* scratch,
+                         hipStream_t st);
 
 // Tx ZMQ framing (emurx_txzmq.hip): see emurx_tx_zmq_dev.  scratch: emurx_txz_scratch_bytes(n).
 size_t emurx_txz_scratch_bytes(uint32_t n);

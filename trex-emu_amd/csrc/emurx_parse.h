@@ -1030,24 +1030,38 @@ __device__ __forceinline__ CInfo client_info(const emurx_dev_tables& T, uint32_t
 // CClient.IsUnicastToMe client_ctx.go:389-398 (frames here are always > 6 bytes) compares the
 // frame's destination with the client's MAC, which the IP slots carry (IpHit)
 
-// Go 1.18 net.IP.IsLinkLocalUnicast / IsGlobalUnicast for a 16-byte address (words LE)
-__device__ __forceinline__ bool ip6_local_or_global(const uint32_t w[4]) {
-    uint32_t b0 = w[0] & 0xff, b1 = (w[0] >> 8) & 0xff;
-    bool v4in6 = w[0] == 0 && w[1] == 0 && (w[2] & 0xffff) == 0 && (w[2] >> 16) == 0xffffu;
-    if (v4in6) {
-        uint32_t v = w[3], c0 = v & 0xff, c1 = (v >> 8) & 0xff;
-        bool ll = c0 == 169 && c1 == 254;
-        if (ll) return true;
-        if (v == 0xffffffffu || v == 0 || c0 == 127 || (c0 & 0xf0) == 0xe0) return false;
-        return true;
-    }
-    bool ll = b0 == 0xfe && (b1 & 0xc0) == 0x80;
-    if (ll) return true;
-    if ((w[0] | w[1] | w[2] | w[3]) == 0) return false;                      // unspecified
-    if (w[0] == 0 && w[1] == 0 && w[2] == 0 && w[3] == 0x01000000u) return false;  // ::1
-    if (b0 == 0xff) return false;                                            // multicast
-    return true;
+// Go 1.18 net.IP predicates for a 16-byte address (words LE).  An IPv4-mapped address
+// (::ffff:a.b.c.d, net.IP.To4) is read as the IPv4 address it holds.  The rules are Go's standard
+// library (net/ip.go), not the reference tree; no capture of the reference pins them.
+__device__ __forceinline__ bool ip6_v4mapped(const uint32_t w[4]) {
+    return w[0] == 0 && w[1] == 0 && (w[2] & 0xffff) == 0 && (w[2] >> 16) == 0xffffu;
 }
+// IsUnspecified: :: or ::ffff:0.0.0.0
+__device__ __forceinline__ bool ip6_unspecified(const uint32_t w[4]) {
+    return w[0] == 0 && w[1] == 0 && w[3] == 0 && (w[2] == 0 || w[2] == 0xffff0000u);
+}
+// IsMulticast: ff00::/8, or 224.0.0.0/4 mapped
+__device__ __forceinline__ bool ip6_multicast(const uint32_t w[4]) {
+    return ip6_v4mapped(w) ? (w[3] & 0xf0) == 0xe0 : (w[0] & 0xff) == 0xff;
+}
+// IsLinkLocalUnicast: fe80::/10, or 169.254.0.0/16 mapped
+__device__ __forceinline__ bool ip6_link_local(const uint32_t w[4]) {
+    if (ip6_v4mapped(w)) return (w[3] & 0xffffu) == (169u | 254u << 8);
+    return (w[0] & 0xff) == 0xfe && ((w[0] >> 8) & 0xc0) == 0x80;
+}
+// IsGlobalUnicast: not the IPv4 broadcast, unspecified, loopback, multicast or link-local
+__device__ __forceinline__ bool ip6_global(const uint32_t w[4]) {
+    if (ip6_v4mapped(w)) {
+        const uint32_t v = w[3], c0 = v & 0xff;
+        return !(v == 0xffffffffu || v == 0 || c0 == 127 || (c0 & 0xf0) == 0xe0 || (v & 0xffffu) == (169u | 254u << 8));
+    }
+    if ((w[0] | w[1] | w[2] | w[3]) == 0) return false;                            // unspecified
+    if (w[0] == 0 && w[1] == 0 && w[2] == 0 && w[3] == 0x01000000u) return false;  // ::1
+    if ((w[0] & 0xff) == 0xff) return false;                                       // multicast
+    return !ip6_link_local(w);
+}
+// IsLinkLocalUnicast || IsGlobalUnicast (CLookupByIPv6LocalGlobal)
+__device__ __forceinline__ bool ip6_local_or_global(const uint32_t w[4]) { return ip6_link_local(w) || ip6_global(w); }
 // PluginDhcpNs.GetMacFromDhcp dhcp.go:863-891 + DHCPv4.DecodeFromBytes dhcpv4.go:125-172
 template <class S>
 __device__ bool dhcp_chaddr(const S& s, uint32_t len, const Rec& r, uint32_t& lo, uint32_t& hi) {

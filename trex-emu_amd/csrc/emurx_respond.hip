@@ -1,12 +1,17 @@
-// emurx_respond.hip — the three stateless answers on the device (gfx950): the ARP reply to a
+// emurx_respond.hip — the stateless answers on the device (gfx950): the ARP reply to a
 // request for a client's IPv4 (src/emu/plugins/arp/arp.go:904-933 -> Respond :776-790), the
-// ICMPv4 echo reply (plugins/icmp/icmp.go:396-461 -> HandleEcho :289-325) and the ICMPv6 echo
-// reply (plugins/ipv6/ipv6.go:465-504 -> HandleEcho :315-357).  emurx_respond_dev, three launches:
+// ICMPv4 echo reply (plugins/icmp/icmp.go:396-461 -> HandleEcho :289-325), the ICMPv6 echo
+// reply (plugins/ipv6/ipv6.go:465-504 -> HandleEcho :315-357) and the neighbour advertisement
+// to a neighbour solicitation (plugins/ipv6/nd.go:1546-1685 -> NdClientCtx.Respond :1220-1253).
+// emurx_respond_dev / emurx_respond_kinds_dev, three launches:
 //   k_rsp_decide   one frame per lane: the record (32 B) says whether the frame is a candidate
-//                  (status OK, lookup EMURX_LK_CLIENT, callback arp / icmp / icmpv6); only a
-//                  candidate's descriptor and a few header bytes are read (ARP: one probe of the
-//                  IPv4 table).  Outcome and reply length per frame; per 256-frame tile the
-//                  replies, their 16-byte rows and the DROP_MCAST / HOST counts.
+//                  (status OK; lookup EMURX_LK_CLIENT, callback arp / icmp / icmpv6; or lookup
+//                  EMURX_LK_NS_LEVEL, callback icmpv6: a neighbour solicitation if its type says
+//                  so; each only if `kinds` selects it); only a candidate's descriptor and a few
+//                  header bytes are read (ARP: one probe of the IPv4 table; a solicitation: its
+//                  addresses as 16-byte spans, one probe of the MAC or the IPv6 table, the client
+//                  info for an RA prefix).  Outcome and reply length per frame; per 256-frame tile
+//                  the replies, their 16-byte rows and the DROP_MCAST / HOST counts.
 //   k_rsp_scan     one workgroup: exclusive scan of the tiles' replies and rows, d_info.
 //   k_rsp_emit     one workgroup per tile that has a reply: ordinals and byte offsets by a scan
 //                  of the tile's plans in LDS, the descriptors, then the tile's output rows dealt
@@ -15,8 +20,9 @@
 //                  funnel-shifted; shifted by the stripped extension headers from l3 + 40 on),
 //                  patched in registers: the swapped Ethernet and IP addresses, which the frame's
 //                  own lane put into LDS once per reply, and at most six rewritten bytes (type,
-//                  checksum, payload length, next header).  The ARP reply (42-50 B, built from the
-//                  template) is written by its frame's own lane.
+//                  checksum, payload length, next header).  The ARP reply (42-50 B) and the
+//                  neighbour advertisement (86-94 B, six rows, checksummed in registers), both
+//                  built from their templates, are written by their frame's own lane.
 // A batch without candidates costs the read of d_rec and one outcome byte per frame: the emit
 // workgroups of tiles without a reply leave after one 8-byte load.
 #include <hip/hip_runtime.h>
@@ -65,11 +71,20 @@ __device__ __forceinline__ IpHit rsp_probe_ip4(const emurx_dev_tables& T, uint32
 
 // The record's words (emurx_rec): ns, client, vlan0, vlan1, vport | l3 << 16, l4 | l7 << 16,
 // l7_len | next_hdr << 16 | proto << 24, status | flags << 8 | rsv << 16
-__device__ __forceinline__ bool rsp_candidate(const uint4& b) {
-    const uint32_t proto = b.z >> 24, status = b.w & 0xff, lk = (b.w >> (8 + EMURX_FLAG_LK_SHIFT)) & 7u;
-    return status == EMURX_ST_OK && lk == EMURX_LK_CLIENT &&
-           (proto == EMURX_CB_ARP || proto == EMURX_CB_ICMP || proto == EMURX_CB_ICMPV6);
+__device__ __forceinline__ uint32_t rsp_lk(const uint4& b) { return (b.w >> (8 + EMURX_FLAG_LK_SHIFT)) & 7u; }
+template <bool kNd>  // kNd: kinds has EMURX_RSPK_ND
+__device__ __forceinline__ bool rsp_candidate(const uint4& b, uint32_t kinds) {
+    const uint32_t proto = b.z >> 24, status = b.w & 0xff, lk = rsp_lk(b);
+    if (status != EMURX_ST_OK) return false;
+    if (lk == EMURX_LK_CLIENT)
+        return (proto == EMURX_CB_ARP && (kinds & EMURX_RSPK_ARP)) || (proto == EMURX_CB_ICMP && (kinds & EMURX_RSPK_ICMP)) ||
+               (proto == EMURX_CB_ICMPV6 && (kinds & EMURX_RSPK_ICMPV6));
+    return kNd && lk == EMURX_LK_NS_LEVEL && proto == EMURX_CB_ICMPV6;
 }
+__device__ __forceinline__ bool rsp_is_reply(uint32_t outcome) {
+    return (outcome >= EMURX_RSP_ARP && outcome <= EMURX_RSP_ICMPV6) || outcome == EMURX_RSP_ND;
+}
+__device__ __forceinline__ void rsp_load16(uintptr_t F, uint32_t flen, int s, uint32_t o[4]);
 
 // The decision for a candidate frame.  Header offsets that do not fit the frame (no record of
 // emurx_classify_dev for these descriptors has them) give EMURX_RSP_HOST: never guess.
@@ -106,12 +121,82 @@ __device__ RspPlan rsp_decide(const uint8_t* __restrict__ frames, const emurx_de
     return {EMURX_RSP_ICMPV6, len - strip};
 }
 
-// tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows
-__global__ __launch_bounds__(kBlock) void k_rsp_decide(const uint8_t* __restrict__ frames,
-                                                       const emurx_desc* __restrict__ desc,
-                                                       const emurx_rec* __restrict__ rec, uint32_t n,
-                                                       const emurx_dev_tables T, uint32_t* __restrict__ plan,
-                                                       uint2* __restrict__ tsum, uint8_t* __restrict__ outcome) {
+// The client that answers a solicitation for target t (words LE), and its MAC (nd.go:1626-1678).
+// EUI-64 target: CLookupByMac of the extracted MAC + IsValidPrefix (client_ctx.go:279-295);
+// otherwise, a global target: CLookupByIPv6.  Then the client's ipv6 plugin.
+struct RspNdHit {
+    bool ok;
+    uint32_t mlo, mhi;
+};
+__device__ __forceinline__ bool rsp_nd_eui(const uint32_t t[4]) { return (t[2] >> 24) == 0xffu && (t[3] & 0xffu) == 0xfeu; }
+__device__ __forceinline__ RspNdHit rsp_nd_ip6(const emurx_dev_tables& T, uint32_t ns, uint32_t tk, const uint32_t t[4]) {
+    const uint32_t bk = emurx_ip6_hash(tk, t[0], t[1], t[2], t[3]) & T.ip6_mask;
+    const IpHit h = resolve_ip6(T, bk, ld_bucket(T.ip6_tab, bk), ns, t);
+    return {h.cid != EMURX_ID_NONE && ((h.mhip >> 16) & (1u << EMURX_PLUG_IPV6)), h.mlo, h.mhip & 0xffffu};
+}
+__device__ RspNdHit rsp_nd_client(const emurx_dev_tables& T, uint32_t ns, uint32_t tk, const uint32_t t[4], bool global) {
+    if (!rsp_nd_eui(t)) return global ? rsp_nd_ip6(T, ns, tk, t) : RspNdHit{false, 0, 0};
+    const uint2 m = eui_mac(t[2], t[3]);
+    if (m.x == 0 && m.y == 0) return {false, 0, 0};  // MACKey.IsZero never matches
+    const uint32_t bk = emurx_mac_hash(tk, m.x, m.y) & T.mac_mask;
+    const uint2 c = resolve_mac(T, bk, ld_bucket(T.mac_tab, bk), ns, m.x, m.y);
+    if (c.x == EMURX_ID_NONE) return {false, 0, 0};
+    if (!(t[0] == 0x000080feu && t[1] == 0)) {  // not fe80::/64: the client's RA prefix, length 64
+        const CInfo ci = client_info(T, c.x);
+        if (!((ci.ra & 1u) && ((ci.ra >> 8) & 0xff) == 64 && ci.ra0 == t[0] && ci.ra1 == t[1])) return {false, 0, 0};
+    }
+    return {(c.y & (1u << EMURX_PLUG_IPV6)) != 0, m.x, m.y};
+}
+
+// The decision for a neighbour solicitation candidate (nd.go:1546-1685; the rule with its
+// citations is in include/emu_rx.h).  A reply if and only if the Go handler would reach
+// nd.Respond; HOST where a lane cannot cheaply decide.
+__device__ RspPlan rsp_decide_nd(const uint8_t* __restrict__ frames, const emurx_desc& d, const uint4& a, const uint4& b,
+                                 const emurx_dev_tables& T) {
+    const uint32_t l3 = b.x >> 16, l4 = b.y & 0xffffu, len = d.len;
+    const uint8_t* f = frames + d.off;
+    if (d.pad == EMURX_DESC_HOLE) return {EMURX_RSP_NONE, 0};
+    if (l3 < 14 || l3 + 40 > l4 || l4 + 4 > len) return {EMURX_RSP_HOST, 0};
+    if (gld1(f + l4) != 135 || gld1(f + l4 + 1) != 0) return {EMURX_RSP_NONE, 0};
+    if (len - (l4 + 4) < 20) return {EMURX_RSP_NONE, 0};  // pktRxErrTooShort
+    // the options are the rest of the frame: none, or one source link-layer address
+    const uint32_t nopt = len - (l4 + 24);
+    if (nopt > 8) return {EMURX_RSP_HOST, 0};
+    if (nopt != 0 && nopt != 8) return {EMURX_RSP_NONE, 0};
+    const uintptr_t F = (uintptr_t)f;
+    uint32_t w[4];
+    const bool slla = nopt == 8;
+    if (slla) {
+        rsp_load16(F, len, (int)(l4 + 24), w);  // w[0], w[1]: the option
+        if ((w[0] & 0xffffu) != 0x0101u) return {EMURX_RSP_NONE, 0};
+        if ((w[0] >> 16) == 0 && w[1] == 0) return {EMURX_RSP_NONE, 0};
+    }
+    if (gld1(f + l3 + 7) != 255) return {EMURX_RSP_NONE, 0};
+    rsp_load16(F, len, (int)(l3 + 8), w);  // the source
+    if (ip6_unspecified(w)) {
+        if (slla) return {EMURX_RSP_NONE, 0};
+        rsp_load16(F, len, (int)(l3 + 24), w);  // the destination
+        if (!ip6_multicast(w)) return {EMURX_RSP_NONE, 0};
+    }
+    rsp_load16(F, len, (int)(l4 + 8), w);  // the target
+    if (ip6_unspecified(w) || ip6_multicast(w)) return {EMURX_RSP_NONE, 0};
+    const bool global = ip6_global(w);
+    if (!(ip6_link_local(w) || global)) return {EMURX_RSP_NONE, 0};
+    const uint32_t tk = emurx_tk_hash(b.x & 0xffffu, a.z, a.w);
+    if (!rsp_nd_client(T, a.x, tk, w, global).ok) return {EMURX_RSP_NONE, 0};
+    return {EMURX_RSP_ND, 86u + 4u * ((a.z != 0) + (a.w != 0))};
+}
+
+// tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows.
+// kNd: whether the call answers solicitations; without them (emurx_respond_dev) the kernel holds
+// none of that path.  Eight waves per SIMD asked for: left to itself the compiler spends 106 SGPRs
+// on the nested divergent branches of the (cold) solicitation path, one wave per SIMD less for
+// every batch.
+template <bool kNd>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_rsp_decide(
+    const uint8_t* __restrict__ frames, const emurx_desc* __restrict__ desc, const emurx_rec* __restrict__ rec, uint32_t n,
+    uint32_t kinds, const emurx_dev_tables T, uint32_t* __restrict__ plan, uint2* __restrict__ tsum,
+    uint8_t* __restrict__ outcome) {
     __shared__ uint32_t s_sum[2];
     if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
     __syncthreads();
@@ -119,13 +204,14 @@ __global__ __launch_bounds__(kBlock) void k_rsp_decide(const uint8_t* __restrict
     RspPlan p{EMURX_RSP_NONE, 0};
     if (i < n) {
         const uint4 b = gld16(reinterpret_cast<const uint4*>(rec + i) + 1);
-        if (rsp_candidate(b)) {
+        if (rsp_candidate<kNd>(b, kinds)) {
             const uint4 a = gld16(reinterpret_cast<const uint4*>(rec + i));
-            p = rsp_decide(frames, desc[i], a, b, T);
+            if (!kNd || rsp_lk(b) == EMURX_LK_CLIENT) p = rsp_decide(frames, desc[i], a, b, T);
+            else p = rsp_decide_nd(frames, desc[i], a, b, T);
         }
         if (outcome) outcome[i] = (uint8_t)p.outcome;
     }
-    const bool reply = p.outcome >= EMURX_RSP_ARP && p.outcome <= EMURX_RSP_ICMPV6;
+    const bool reply = rsp_is_reply(p.outcome);
     const uint32_t c = wave_sum_u32((reply ? 1u : 0u) | (p.outcome == EMURX_RSP_DROP_MCAST ? 1u << 10 : 0u) |
                                     (p.outcome == EMURX_RSP_HOST ? 1u << 20 : 0u));
     const uint32_t r = wave_sum_u32(reply ? (p.len + 15) >> 4 : 0u);
@@ -166,12 +252,13 @@ __device__ __forceinline__ void rsp_block_scan(uint32_t& c, unsigned long long& 
     }
 }
 
-// info: {n_out, bytes needed, count of outcomes 1..6}: the scan writes bytes needed, DROP_MCAST
-// and HOST and zeroes the rest; the emit pass adds n_out, the replies by kind and NOSPC
+// info: {n_out, bytes needed, count of outcomes 1..7, zeros}, info_words (8 or
+// EMURX_RSP_INFO_WORDS) of them: the scan writes bytes needed, DROP_MCAST and HOST and zeroes the
+// rest; the emit pass adds n_out, the replies by kind and NOSPC
 __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restrict__ tsum, uint32_t ntiles,
                                                             uint32_t* __restrict__ tord,
                                                             unsigned long long* __restrict__ trow,
-                                                            unsigned long long* __restrict__ info) {
+                                                            unsigned long long* __restrict__ info, uint32_t info_words) {
     __shared__ uint32_t s_c[kRspScanBlock / kWave][2];
     __shared__ unsigned long long s_r[kRspScanBlock / kWave];
     __shared__ uint32_t s_dh[2];
@@ -208,7 +295,7 @@ __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restr
         atomicAdd(&s_dh[1], host);
     }
     __syncthreads();
-    if (threadIdx.x < 8) {
+    if (threadIdx.x < info_words) {
         const uint32_t k = threadIdx.x;
         info[k] = k == 1 ? rbase * 16ull : k == 2 + EMURX_RSP_DROP_MCAST - 1 ? s_dh[0] : k == 2 + EMURX_RSP_HOST - 1 ? s_dh[1] : 0ull;
     }
@@ -271,18 +358,18 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
     __shared__ RspReply s_rep[kRspTile];
     __shared__ uint32_t s_mac[kRspTile][3];   // an echo reply's first 12 bytes: the Ethernet addresses swapped
     __shared__ uint32_t s_ip[kRspTile][10];   // its IP addresses swapped (8 or 32 bytes) between two pad dwords
-    __shared__ uint32_t s_cnt[5];             // written replies by kind (1..3), NOSPC
+    __shared__ uint32_t s_cnt[8];             // by outcome: written replies by kind (1..3, 7), NOSPC (6)
     const uint32_t t = blockIdx.x;
     const uint2 ts = tsum[t];
     const uint32_t replies = ts.x & 0x3ffu;
     if (!replies) return;  // workgroup-uniform
     const uint32_t lane = lane_id(), wv = threadIdx.x / kWave, i = t * kRspTile + threadIdx.x;
-    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
     const uint32_t ord0 = tord[t];
     const unsigned long long row0 = trow[t];
     const uint32_t p = i < n ? plan[i] : 0u;
     const uint32_t kind = p >> 16, rlen = p & 0xffffu;
-    const bool reply = kind >= EMURX_RSP_ARP && kind <= EMURX_RSP_ICMPV6;
+    const bool reply = rsp_is_reply(kind);
     const uint32_t rows = reply ? (rlen + 15) >> 4 : 0u;
     // ordinal and first row inside the tile: wave scans, then the waves' totals
     uint32_t k = reply ? 1u : 0u, r = rows;
@@ -349,6 +436,82 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
                     if (j < rows) o[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+            } else if (kind == EMURX_RSP_ND) {
+                // the template's advertisement (nd.go:835-865, 1220-1253): the frame's own lane
+                // writes its six rows.  An EUI-64 target names the client's MAC; for any other
+                // target the MAC is the IPv6 slot's (the probe of k_rsp_decide again; on a miss,
+                // as for ARP, the reply keeps the decided length, with a zero MAC)
+                const uintptr_t Fa = (uintptr_t)f;
+                uint32_t tg[4], sa[4], m[4];
+                rsp_load16(Fa, d.len, (int)(l4 + 8), tg);
+                rsp_load16(Fa, d.len, (int)(l3 + 8), sa);
+                rsp_load16(Fa, d.len, 0, m);
+                uint32_t m03, m45;
+                if (rsp_nd_eui(tg)) {
+                    const uint2 em = eui_mac(tg[2], tg[3]);
+                    m03 = em.x;
+                    m45 = em.y;
+                } else {
+                    const RspNdHit h = rsp_nd_ip6(T, a.x, emurx_tk_hash(vport, a.z, a.w), tg);
+                    m03 = h.ok ? h.mlo : 0u;
+                    m45 = h.ok ? h.mhi : 0u;
+                }
+                const bool dad = ip6_unspecified(sa);
+                // the IPv6 packet's 18 words: header, source, destination, 88 00 cs cs, fl 00 00 00,
+                // the target, 02 01 + the MAC.  Unicast: from the target to the request's source,
+                // flags 0x60; duplicate address detection: from the client's link-local address
+                // (fe80:: + EUI-64 of the MAC) to ff02::1, flags 0
+                uint32_t P[18];
+                P[0] = 0x00000060u;
+                P[1] = 0xff3a2000u;
+                const uint32_t ll2 = ((m03 & 0xffu) ^ 2u) | (m03 & 0xffff00u) | 0xff000000u;
+                const uint32_t ll3 = 0xfeu | (m03 >> 24) << 8 | m45 << 16;
+                P[2] = dad ? 0x000080feu : tg[0];
+                P[3] = dad ? 0u : tg[1];
+                P[4] = dad ? ll2 : tg[2];
+                P[5] = dad ? ll3 : tg[3];
+                P[6] = dad ? 0x000002ffu : sa[0];
+                P[7] = dad ? 0u : sa[1];
+                P[8] = dad ? 0u : sa[2];
+                P[9] = dad ? 0x01000000u : sa[3];
+                P[10] = 0x00000088u;
+                P[11] = dad ? 0u : 0x60u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) P[12 + j] = tg[j];
+                P[16] = 0x00000102u | m03 << 16;
+                P[17] = m03 >> 16 | m45 << 16;
+                // FixIcmpL4Checksum (ip6.go:54-56): the pseudo header (addresses, length 32, next
+                // header 58) and the 32 bytes; every word sits at an even offset, so the sum of
+                // little-endian halves is the byte-swapped sum and its complement goes in as is
+                uint32_t acc = sad16(0x20000000u, sad16(0x3a000000u, 0u));
+#pragma unroll
+                for (int j = 2; j < 18; ++j) acc = sad16(P[j], acc);
+                P[10] |= (~fold16(acc) & 0xffffu) << 16;
+                const uint32_t ntag = (a.z != 0) + (a.w != 0);
+                const uint32_t tag0 = __builtin_bswap32(a.z ? a.z : a.w), tag1 = __builtin_bswap32(a.w);
+                // dst = the request's Ethernet source or 33:33:00:00:00:01, src = the client; from
+                // the EtherType on, the packet sits two bytes off the dword grid
+                const uint32_t d03 = dad ? 0x00003333u : m[1] >> 16 | m[2] << 16, d45 = dad ? 0x0100u : m[2] >> 16;
+                const uint32_t head[3] = {d03, d45 | m03 << 16, m03 >> 16 | m45 << 16};
+                uint32_t body[19];
+                body[0] = 0xdd86u | P[0] << 16;
+#pragma unroll
+                for (int j = 1; j < 18; ++j) body[j] = P[j - 1] >> 16 | P[j] << 16;
+                body[18] = P[17] >> 16;
+                uint4* o = reinterpret_cast<uint4*>(out + off);
+#pragma unroll
+                for (int r4 = 0; r4 < 6; ++r4) {  // rows == 6 for 86, 90 and 94 bytes
+                    uint32_t w[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int j = 4 * r4 + q;
+                        const uint32_t w0 = j < 3 ? head[j] : j < 22 ? body[j - 3] : 0u;
+                        const uint32_t w1 = j < 3 ? head[j] : j == 3 ? tag0 : j < 23 ? body[j - 4] : 0u;
+                        const uint32_t w2 = j < 3 ? head[j] : j == 3 ? tag0 : j == 4 ? tag1 : body[j - 5];
+                        w[q] = ntag == 0 ? w0 : ntag == 1 ? w1 : w2;
+                    }
+                    o[r4] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
             } else {
                 const uint32_t l4n = kind == EMURX_RSP_ICMP ? l4 : l3 + 40;  // the reply's l4
                 const uint32_t ocs = gld1(f + l4 + 2) << 8 | gld1(f + l4 + 3);
@@ -382,13 +545,14 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
         }
         s_row[k] = r;
         s_rep[k] = e;
-        atomicAdd(&s_cnt[fits ? kind : 4u], 1u);
+        atomicAdd(&s_cnt[fits ? kind : (uint32_t)EMURX_RSP_NOSPC], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 5) {  // info[1 + outcome] counts the outcome; info[0] = the replies written
+    if (threadIdx.x < 8) {  // info[1 + outcome] counts the outcome; info[0] = the replies written
+        // (ND is no outcome of the eight-word form: its count is 0 there and info[8] is not touched)
         const uint32_t j = threadIdx.x;
-        const uint32_t c = j ? s_cnt[j] : s_cnt[1] + s_cnt[2] + s_cnt[3];
-        if (c) atomicAdd(&info[j == 0 ? 0u : j == 4 ? 1u + EMURX_RSP_NOSPC : 1u + j], (unsigned long long)c);
+        const uint32_t c = j ? s_cnt[j] : s_cnt[EMURX_RSP_ARP] + s_cnt[EMURX_RSP_ICMP] + s_cnt[EMURX_RSP_ICMPV6] + s_cnt[EMURX_RSP_ND];
+        if (c) atomicAdd(&info[j ? 1u + j : 0u], (unsigned long long)c);
     }
     // ---- the echo replies' rows, dealt over the lanes
     const uint32_t R = ts.y;
@@ -454,19 +618,22 @@ size_t emurx_rsp_scratch_bytes(uint32_t n) {
 }
 
 int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
-                         const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc, uint32_t* out_src,
-                         uint8_t* outcome, uint64_t* info, void* scratch, hipStream_t st) {
+                         uint32_t kinds, const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc,
+                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, void* scratch,
+                         hipStream_t st) {
     using namespace emurx;
     unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
-    if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 64, st)) ? 0 : -1;
+    if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 8 * (size_t)info_words, st)) ? 0 : -1;
     const uint32_t nt = (n + kRspTile - 1) / kRspTile;
     uint8_t* p = static_cast<uint8_t*>(scratch);
     uint32_t* plan = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)n * 4);
     uint2* tsum = reinterpret_cast<uint2*>(p); p += rsp_align((size_t)nt * 8);
     uint32_t* tord = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)nt * 4);
     unsigned long long* trow = reinterpret_cast<unsigned long long*>(p);
-    hipError_t e = emurx_launch(k_rsp_decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, plan, tsum, outcome);
-    if (e == hipSuccess) e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, tsum, nt, tord, trow, inf);
+    const auto decide = (kinds & EMURX_RSPK_ND) ? k_rsp_decide<true> : k_rsp_decide<false>;
+    hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, plan, tsum, outcome);
+    if (e == hipSuccess)
+        e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, tsum, nt, tord, trow, inf, info_words);
     if (e == hipSuccess)
         e = emurx_launch(k_rsp_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, plan, tsum, tord, trow, out,
                          (unsigned long long)cap, out_desc, out_src, outcome, inf);

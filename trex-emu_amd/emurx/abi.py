@@ -113,6 +113,10 @@ ZMQ_TX_BURST, ZMQ_TX_MAX_BUFFER, ZMQ_PKT_MAGIC = 64, 32768, 0xAA  # veth_zmq.go:
 TX_ZMQ_MAX_FRAMES = 1 << 26  # EMURX_TX_ZMQ_MAX_FRAMES: n of tx_zmq_dev / respond_dev is below it
 # enum emurx_rsp: the per-frame outcome of emurx_respond_dev
 RSP_NONE, RSP_ARP, RSP_ICMP, RSP_ICMPV6, RSP_DROP_MCAST, RSP_HOST, RSP_NOSPC = range(7)
+RSP_ND = 7  # neighbour advertisement written (emurx_respond_kinds_dev with RSPK_ND)
+# EMURX_RSPK_*: the answers emurx_respond_kinds_dev is asked for; its d_info has RSP_INFO_WORDS words
+RSPK_ARP, RSPK_ICMP, RSPK_ICMPV6, RSPK_ND, RSPK_ALL = 1, 2, 4, 8, 15
+RSP_INFO_WORDS = 16
 FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xFFFFFFF0, 0xFFFFFFF1,
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
@@ -224,6 +228,7 @@ SIGNATURES = [
     ("emurx_tx_checksum_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),

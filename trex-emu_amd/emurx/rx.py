@@ -258,15 +258,22 @@ class RxPath:
         return abi.check(self.lib.emurx_tx_zmq_dev(self.h, _addr(frames), _addr(desc), n, _addr(out), cap,
                                                    _addr(msg_off), _addr(info), _stream(stream)), "tx_zmq_dev")
 
-    def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None):
+    def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None,
+                    kinds=None):
         """The ARP / ICMPv4 echo / ICMPv6 echo replies of a classified batch, built on the device
         (include/emu_rx.h emurx_respond_dev): replies compacted in rx order into `out` at 16-byte
         aligned offsets, out_desc / out_src [n] (the descriptors tx_zmq_dev takes, the rx frame
         index), outcome u8 [n] (abi.RSP_*, or None), info u64[8] {n_out, bytes needed, frames per
-        outcome 1..6}."""
-        return abi.check(self.lib.emurx_respond_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, _addr(out), cap,
-                                                    _addr(out_desc), _addr(out_src), _addr(outcome), _addr(info),
-                                                    _stream(stream)), "respond_dev")
+        outcome 1..6}.  With kinds (abi.RSPK_*, emurx_respond_kinds_dev) only the selected answers
+        are built, the neighbour advertisement (RSPK_ND) among them, and info is
+        u64[abi.RSP_INFO_WORDS] {n_out, bytes needed, frames per outcome 1..7, zeros}."""
+        if kinds is None:
+            return abi.check(self.lib.emurx_respond_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, _addr(out), cap,
+                                                        _addr(out_desc), _addr(out_src), _addr(outcome), _addr(info),
+                                                        _stream(stream)), "respond_dev")
+        return abi.check(self.lib.emurx_respond_kinds_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds,
+                                                          _addr(out), cap, _addr(out_desc), _addr(out_src), _addr(outcome),
+                                                          _addr(info), _stream(stream)), "respond_kinds_dev")
 
     # ---- Namespace-partitioned exchange ---------------------------------------------------
     def classify_route_dev(self, frames, desc, n: int, rec, qlist, qcap: int, tile_cnt, hist, n_parts: int,
