@@ -688,10 +688,11 @@ int emurx_kernel_times(emurx_t* h, float* batch_ms, uint32_t cap, uint32_t* n_ou
    provenance, printed by the Python binding when it loads the library. */
 const char* emurx_build_id(void);
 
-/* LDS staging slab (bytes per wave) of the most recent k_rx launch: 7168 or 6144 (0 before
-   the first).  Chosen per launch from sampled feedback of earlier launches (a wave whose
-   frames span 6-7 KiB fits only the wider slab); EMURX_STAGE=wide|narrow in the environment
-   at emurx_open forces one.  Results never depend on it.  No ABI replacement: a tuning
+/* LDS staging slab (bytes per wave) of the most recent k_rx launch: 7168, 6144 or 5120 (0
+   before the first).  Chosen per launch from sampled feedback of earlier launches (a wave whose
+   frames span 6-7 KiB fits only the widest slab; 5120 once two samples in a row saw at most
+   1 % of the waves over 5 KiB); EMURX_STAGE=wide|narrow|tight in the environment at emurx_open
+   forces one.  Results never depend on it.  No ABI replacement: a tuning
    observable of this implementation. */
 uint32_t emurx_last_stage(const emurx_t* h);
 /* LDS image (bytes per wave) of the most recent tx framing write (emurx_tx_zmq_dev): 6144,

@@ -14,7 +14,7 @@ and the interval (last end - first start) / launches, which is what the bench's 
 around a group measures.  With --batches <= --streams there is no replay group: pass
 `--no-replay` as the third argument.  `--kernel <text>` keeps only the k_rx dispatches whose name
 holds <text> (the default command also runs config D's exchange after the headline: pass
-`--kernel "k_rx<1, 6144u>"` for config B's narrow-slab launches).  `--trim-isolated` drops the
+`--kernel "k_rx<1, 5120u>"` for config B's tight-slab launches).  `--trim-isolated` drops the
 trailing isolated launches of the default line's host_inclusive block (ingest batches, each on its
 own after its copies).
 """

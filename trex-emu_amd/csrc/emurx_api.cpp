@@ -219,10 +219,15 @@ struct emurx_ctx {
     // memory behind itself (stream order, an event, no synchronisation), and the first
     // launch after the copy has landed decides.  The kernel
     // writing host memory directly was tried: host reads of lines the GPU keeps writing made
-    // some launches 5x slower.  EMURX_STAGE=wide|narrow forces one size (tests, A/B).
-    DevBuf<uint32_t> d_stage_fb;  // 64 sampled tiles x 4 waves: gen << 2 | has_frames << 1 | mid
+    // some launches 5x slower.  The tight 5 KiB slab runs 7 workgroups per CU (64-byte frames:
+    // 4,352 B per wave); a wave over 5 KiB then takes the window path with an 80-byte window,
+    // so it is chosen by the same 1 % rule on the waves over 5 KiB, and only at the second
+    // decision in a row that sees it eligible, the first of which chose narrow: one sample is
+    // too little evidence.  Any decision that sees more than 1 % of the waves over 5 KiB leaves
+    // it at once.  EMURX_STAGE=wide|narrow|tight forces one size (tests, A/B).
+    DevBuf<uint32_t> d_stage_fb;  // 64 sampled tiles x 4 waves: gen << 3 | over_5k << 2 | has_frames << 1 | mid
     PinBuf<uint32_t> stage_fb;    // its copy
-    uint32_t stage_gen = 0, stage_mode = 0;  // 0 auto, 1 wide, 2 narrow
+    uint32_t stage_gen = 0, stage_mode = 0;  // 0 auto, 1 wide, 2 narrow, 3 tight
     bool stage_copy = false, stage_pending = false;
     uint32_t stage_copy_gen = 0;
     // launches between copy-backs: 8, doubled after each decision that repeats the one before
@@ -231,7 +236,8 @@ struct emurx_ctx {
     // overlap with the next launch): config B's 20-step command ran 2-3 % slower with one per 8
     uint32_t stage_every = 8, stage_same = 0;
     hipEvent_t stage_ev = nullptr;
-    bool stage_narrow = false;
+    uint32_t stage_bytes = emurx::kStageWide;  // the slab of the next launch (emurx::kStage*)
+    bool stage_tight_ok = false;        // the last decision saw the tight slab eligible
     uint32_t last_stage = 0;
 
     // the Namespace-owner exchange's communicator (emurx_comm.cpp), or none
@@ -396,44 +402,51 @@ int prepare_read(emurx_t* h, hipStream_t st) {
 uint32_t ntiles(uint32_t n) { return (n + EMURX_QUEUE_TILE - 1) / EMURX_QUEUE_TILE; }
 size_t queue_cap(uint32_t n) { return (size_t)ntiles(n) * EMURX_QUEUE_TILE; }
 
-// the staging slab of the next k_rx launch (see emurx_ctx::stage_fb); advances stage_gen
-bool choose_stage_(emurx_t* h) {
+// the staging slab of the next k_rx launch in bytes (see emurx_ctx::stage_fb); advances
+// stage_gen (29 bits: the feedback word's other three are the wave's facts)
+constexpr uint32_t kStageGenMask = 0x1fffffffu;
+uint32_t choose_stage_(emurx_t* h) {
     ++h->stage_gen;
-    h->stage_gen &= 0x3fffffffu;
-    if (h->stage_mode) return h->stage_mode == 2;
+    h->stage_gen &= kStageGenMask;
+    if (h->stage_mode) return h->stage_mode == 3 ? emurx::kStageTight : h->stage_mode == 2 ? emurx::kStageNarrow : emurx::kStageWide;
     // decide as soon as the last copy-back has landed (an event query, no waiting)
     if (h->stage_pending && hipEventQuery(h->stage_ev) == hipSuccess) {  // "not ready" is no error
         h->stage_pending = false;
         // the sampled waves of the 16 launches up to the copied one (a 1M-frame launch
         // rewrites all 256 words, a small one only the first few)
-        uint32_t waves = 0, mid = 0;
+        uint32_t waves = 0, mid = 0, over = 0;
         for (int i = 0; i < 256; ++i) {
             const uint32_t w = h->stage_fb.p[i];
-            const uint32_t age = (h->stage_copy_gen - (w >> 2)) & 0x3fffffffu;
-            if ((w >> 2) && age < 16) {
+            const uint32_t age = (h->stage_copy_gen - (w >> 3)) & kStageGenMask;
+            if ((w >> 3) && age < 16) {
                 waves += (w >> 1) & 1;
                 mid += w & 1;
+                over += (w >> 2) & 1;
             }
         }
         // a wave in the 6-7 KiB band costs several staged waves on the window path; below
         // 1% of the sampled waves the extra workgroup per CU wins (configs B, E), above it
         // loses (C)
         if (waves) {
-            const bool narrow = mid * 100 <= waves;
-            if (narrow != h->stage_narrow) {
+            // over counts the band's waves too, so an eligible sample is a narrow one as well
+            const bool narrow = mid * 100 <= waves, tight_ok = over * 100 <= waves;
+            const uint32_t bytes = !narrow ? emurx::kStageWide
+                                   : tight_ok && h->stage_tight_ok ? emurx::kStageTight : emurx::kStageNarrow;
+            h->stage_tight_ok = tight_ok;
+            if (bytes != h->stage_bytes) {
                 h->stage_same = 0;
                 h->stage_every = 8;
             } else if (++h->stage_same >= 2 && h->stage_every < 256) {
                 h->stage_every *= 2;
             }
-            h->stage_narrow = narrow;
+            h->stage_bytes = bytes;
         }
     }
     // the first launch and then at most every stage_every-th copies its samples back
     if (!h->stage_pending &&
-        (!h->stage_copy_gen || ((h->stage_gen - h->stage_copy_gen) & 0x3fffffffu) >= h->stage_every))
+        (!h->stage_copy_gen || ((h->stage_gen - h->stage_copy_gen) & kStageGenMask) >= h->stage_every))
         h->stage_copy = true;
-    return h->stage_narrow;
+    return h->stage_bytes;
 }
 int stage_copy_back(emurx_t* h, hipStream_t st) {
     if (!h->stage_copy) return 0;
@@ -445,10 +458,8 @@ int stage_copy_back(emurx_t* h, hipStream_t st) {
     h->stage_copy_gen = h->stage_gen;
     return 0;
 }
-bool choose_stage(emurx_t* h) {
-    const bool narrow = choose_stage_(h);
-    h->last_stage = narrow ? 6144u : 7168u;
-    return narrow;
+uint32_t choose_stage(emurx_t* h) {
+    return h->last_stage = choose_stage_(h);
 }
 
 // route scratch of stream st for batches of up to max_frames: per-tile counts, per-group sums
@@ -508,8 +519,8 @@ int run_dev(emurx_t* h, const uint8_t* frames, const emurx_desc* desc, uint32_t 
         h->ev_head = (s + 1) % h->slots;
         h->ev_count = std::min(h->ev_count + 1, h->slots);
     }
-    const bool narrow = choose_stage(h);
-    int r = emurx_launch_batch(frames, desc, n, T, kind, *out, st, ev, narrow, h->d_stage_fb.p, h->stage_gen, rt);
+    const uint32_t stage = choose_stage(h);
+    int r = emurx_launch_batch(frames, desc, n, T, kind, *out, st, ev, stage, h->d_stage_fb.p, h->stage_gen, rt);
     if (!r) r = stage_copy_back(h, st);
     return r ? EMURX_EDEVICE : EMURX_OK;
 }
@@ -669,8 +680,8 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     if (emurx_launch_zmq_walk(s.d_buf.p, s.d_ctl.p, nmsg, s.d_desc.p, s.d_stat.p, st)) return EMURX_EDEVICE;
     if (n) {
         const emurx_dev_out o{s.d_rec.p, s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, s.d_hist.p};
-        const bool narrow = choose_stage(h);
-        if (emurx_launch_batch(s.d_buf.p, s.d_desc.p, n, h->tables(), true, o, st, nullptr, narrow,
+        const uint32_t stage = choose_stage(h);
+        if (emurx_launch_batch(s.d_buf.p, s.d_desc.p, n, h->tables(), true, o, st, nullptr, stage,
                                h->d_stage_fb.p, h->stage_gen) ||
             stage_copy_back(h, st))
             return EMURX_EDEVICE;
@@ -810,7 +821,7 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
     int rc = bind(h);
     if (rc) { delete h; return rc; }
     if (!EMURX_HIP_OK(hipStreamCreate(&h->stream))) { delete h; return EMURX_EDEVICE; }
-    if (const char* e = getenv("EMURX_STAGE")) h->stage_mode = !strcmp(e, "wide") ? 1 : !strcmp(e, "narrow") ? 2 : 0;
+    if (const char* e = getenv("EMURX_STAGE")) h->stage_mode = !strcmp(e, "wide") ? 1 : !strcmp(e, "narrow") ? 2 : !strcmp(e, "tight") ? 3 : 0;
     if (const char* e = getenv("EMURX_INGEST_SMALL")) h->ingest_small = strcmp(e, "0") != 0;
     if (const char* e = getenv("EMURX_TXZ"))
         h->txz_mode = !strcmp(e, "wide") ? EMURX_TXZ_WIDE : !strcmp(e, "narrow") ? EMURX_TXZ_NARROW

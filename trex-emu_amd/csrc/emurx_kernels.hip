@@ -147,8 +147,16 @@ __device__ __forceinline__ uint64_t match_lanes(uint32_t v, uint64_t act) {
     return m;
 }
 
-// The workgroup's small LDS arrays of one tile
-struct TileLds {
+// The workgroup's small LDS arrays of one tile.  kPark (the tight slab's classify build): a
+// second dword per lane for the record fields parked across the table probes (tile_body)
+template <bool kPark>
+struct TilePark {
+    uint32_t park[kWaves][kWave];
+};
+template <>
+struct TilePark<false> {};
+template <bool kPark>
+struct TileLds : TilePark<kPark> {
     uint32_t wcnt[kWaves][16];                   // queue counts per wave
     uint32_t csum[kWaves][kWave];                // window path: span sums; then the histogram rows
     uint32_t rcnt[kWaves][EMURX_MAX_PARTS];      // Namespace owners
@@ -162,8 +170,15 @@ struct TileLds {
 // workgroup's kWaves slabs of kStage bytes): parse, classify, record, queue segment, counts.
 template <int kKind, uint32_t kStage>
 __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 dd, Stage sg, const uint32_t* slab,
-                                          TileLds& L, const TileOffLoads& tol, const unsigned long long* pre = nullptr) {
+                                          TileLds<kKind == 1 && kStage == kStageTight>& L, const TileOffLoads& tol,
+                                          const unsigned long long* pre = nullptr) {
     constexpr bool kClassify = kKind == 1;
+    // 7 workgroups per CU leave a lane 72 VGPRs, and the two 64-byte buckets of the probes take
+    // 32 of them: the tight classify build parks the record fields that the lookups do not read
+    // in the wave's own LDS rows from the parse to the end of the lookups (classify_parked below:
+    // two LDS writes and reads per lane, no memory trip, 9 VALU instructions per wave; the wider
+    // builds have the registers and keep the fields where they are)
+    constexpr bool kParkRec = kClassify && kStage == kStageTight;
     constexpr uint32_t kWinVec = kStage / 16 / kWave;
     const emurx_dev_tables& T = a.T;
     const emurx_route_args& rt = a.rt;
@@ -174,7 +189,10 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     static_assert(EMURX_HIST_BINS == kWave, "one histogram bin per lane");
     uint32_t (*s_hist)[EMURX_HIST_BINS] = L.csum;
 
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wv = tid / kWave;
+    const uint32_t tid = threadIdx.x, lane = lane_id();
+    // the tight slab's 72 registers: the wave's number as a scalar, so that what derives from
+    // it (its slab, its LDS rows) is scalar arithmetic instead of a register per lane each
+    const uint32_t wv = kStage == kStageTight ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / kWave)) : tid / kWave;
 #if EMURX_STAMP
     // entry, descriptors, staging landed: taken by the caller
     unsigned long long st_[10] = {pre ? pre[0] : 0, pre ? pre[1] : 0, pre ? pre[2] : 0, 0, 0, 0, 0, 0, 0, 0};
@@ -191,11 +209,12 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     const bool valid = (dd.y >> 24) != EMURX_DESC_HOLE;
     const uint32_t off = dd.x, len = dd.y & 0xffff, vport = (dd.y >> 16) & 0xff;
     // stage-size feedback from every 64th tile (the launcher's choice, emurx_api.cpp): one
-    // word per wave {gen, the wave has frames, its range fits the wide slab only}
+    // word per wave {gen, its range exceeds the tight slab, the wave has frames, its range fits
+    // the wide slab only}
     if (a.fb && (tile & 63) == 0 && lane == 0) {
         const uint32_t bytes = sg.nvec * 16;
         const uint32_t mid = bytes > kStageNarrow && bytes <= kStageWide;
-        a.fb[((tile >> 6) & 63) * kWaves + wv] = (a.gen << 2) | ((sg.nvec > 0) << 1) | mid;
+        a.fb[((tile >> 6) & 63) * kWaves + wv] = (a.gen << 3) | ((bytes > kStageTight) << 2) | ((sg.nvec > 0) << 1) | mid;
     }
 
     Rec r;
@@ -209,12 +228,67 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     uint4* ltail = wslab + kWave * 2 + lane * 3;
     static_assert(kStage >= kWave * (32 + 48), "a wave's lookup heads and tails fit its slab");
     uint32_t tun = 0;  // kKind 2: the frame's tail units (0, 1 or 3)
+    // classify() with l4 | l7 << 16 and l7len | nh << 16 | flags << 24 | status << 27 parked in
+    // LDS across it (kParkRec; the csum row is free between the span sums and the histogram; of
+    // flags the parse sets bit 0 alone, so the lookups start from 0 and it is or-ed back; the
+    // lookups run for status OK only and do not read it).
+    // The volatile reads keep the compiler from forwarding the stored values, which would hold
+    // them in registers after all.  The rare readers inside the lookups (the flow probe's tuple,
+    // IsUnicastToMe's destination MAC) read the parked words and the frame again; on the window
+    // path through a window source built again from the descriptor behind an opaque copy, so the
+    // first one ends with the lookup key instead of holding its five registers across the probes
+    auto classify_parked = [&](const auto& s) {
+        if constexpr (kParkRec) {
+            typedef std::decay_t<decltype(s)> S;
+            volatile uint32_t* pa = &L.csum[wv][lane];
+            volatile uint32_t* pb = &L.park[wv][lane];
+            *pa = r.l4 | (r.l7 << 16);
+            static_assert(EMURX_FLAG_RTALERT < 8 && EMURX_ST_PANIC_MBUF < 32, "flags and status share the parked byte");
+            *pb = r.l7len | (r.nh << 16) | (r.flags << 24) | (r.status << 27);
+            r.flags = 0;
+            if (r.status == EMURX_ST_OK) {
+                const LKey k = make_key(s, len, r);
+                const uint32_t l3 = r.l3;
+                auto again = [&]() {
+                    if constexpr (std::is_same<S, WinSrc>::value) {
+                        uint32_t o2 = off, l2 = lane;
+                        asm volatile("" : "+v"(o2), "+v"(l2));
+                        const uint32_t h2 = (uint32_t)((uintptr_t)(a.frames + o2) & 15);
+                        return WinSrc{reinterpret_cast<const uint8_t*>(slab), slab, wv * kStage + l2 * 16, h2,
+                                      (uint32_t)min(kWinVec * 16 - h2, len), a.frames + o2};
+                    } else {
+                        return s;
+                    }
+                };
+                resolve(T, r, k,
+                        [&](uint32_t cid) {
+                            Rec q;
+                            q.l3 = l3;
+                            q.l4 = *pa & 0xffffu;
+                            q.nh = (*pb >> 16) & 0xffu;
+                            return flow_probe(T, get_tuple(again(), len, q), cid);
+                        },
+                        [&]() {
+                            const S s2 = again();
+                            return make_uint3(le32(s2, 0), s2.u8(4) | (s2.u8(5) << 8), s2.u8(l3 + 8) == 0xff);
+                        });
+            }
+            const uint32_t wa = *pa, wb = *pb;
+            r.l4 = wa & 0xffffu;
+            r.l7 = wa >> 16;
+            r.l7len = wb & 0xffffu;
+            r.nh = (wb >> 16) & 0xffu;
+            r.flags |= (wb >> 24) & 7u;
+            r.status = wb >> 27;
+        }
+    };
     if (sg.staged) {  // wave-uniform branch
         if (valid) {
             LdsSrc s{reinterpret_cast<const uint8_t*>(slab), slab, wv * kStage + (off - sg.start)};
             parse_flat(s, len, vport, T.cb_mask, r);
             STAMP(3);
-            if (kClassify) classify(s, len, T, r);
+            if constexpr (kParkRec) classify_parked(s);
+            else if (kClassify) classify(s, len, T, r);
             if (kKind == 2) tun = pack_lookup(s, len, r, i, r.status == EMURX_ST_OK, rt.tup_on, lhead, ltail);
         }
     } else {
@@ -224,7 +298,11 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
         if (valid) parse_packet(s, len, vport, T.cb_mask, r);
         coop_checksum_rows(r, a.frames + off, L.csum[wv]);  // the wave's long L4 spans, converged
         STAMP(3);
-        if (valid && kClassify) classify(s, len, T, r);
+        if constexpr (kParkRec) {
+            if (valid) classify_parked(s);
+        } else if (valid && kClassify) {
+            classify(s, len, T, r);
+        }
         if (kKind == 2 && valid) tun = pack_lookup(s, len, r, i, r.status == EMURX_ST_OK, rt.tup_on, lhead, ltail);
     }
     STAMP(4);
@@ -461,9 +539,9 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
 
 // One tile per workgroup: stage, wait, process
 template <int kKind, uint32_t kStage>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStage == kStageNarrow ? 6 : 5))) void k_rx(const RxArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStage == kStageTight ? 7 : kStage == kStageNarrow ? 6 : 5))) void k_rx(const RxArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t slab[kWaves * kStage / 4];
-    __shared__ TileLds L;
+    __shared__ TileLds<kKind == 1 && kStage == kStageTight> L;
     const uint32_t tile = blockIdx.x, wv = threadIdx.x / kWave;
 #if EMURX_STAMP
     unsigned long long pre[3];
@@ -507,7 +585,7 @@ int emurx_launch_apply(const emurx_delta* d, uint32_t n, hipStream_t st) {
 // ---------------------------------------------------------------------------------------
 int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n,
                        const emurx_dev_tables& T, int kind, const emurx_dev_out& out,
-                       hipStream_t st, const hipEvent_t* ev, bool narrow, uint32_t* fb, uint32_t gen,
+                       hipStream_t st, const hipEvent_t* ev, uint32_t stage, uint32_t* fb, uint32_t gen,
                        const emurx_route_args* rt) {
     using namespace emurx;
     hipError_t e = hipSuccess;
@@ -521,9 +599,13 @@ int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n
         const emurx_route_args none{};
         const RxArgs args{frames, desc, n, T, out.rec, out.qlist, out.qcap, out.tile_cnt, hist, out.flow, fb, gen,
                           rt ? *rt : none};
-        auto k = kind == 1 ? (narrow ? k_rx<1, kStageNarrow> : k_rx<1, kStageWide>)
-               : kind == 2 ? (narrow ? k_rx<2, kStageNarrow> : k_rx<2, kStageWide>)
-                           : (narrow ? k_rx<0, kStageNarrow> : k_rx<0, kStageWide>);
+        // every kind has the tight slab: at 7 waves per SIMD (72 VGPRs) kinds 0 and 2 compile
+        // without scratch as they are (58 and 69 VGPRs), kind 1 with its record fields parked
+        // (tile_body kParkRec, 71), so a tight choice never maps to another size
+        const bool narrow = stage == kStageNarrow, tight = stage == kStageTight;
+        auto k = kind == 1 ? (tight ? k_rx<1, kStageTight> : narrow ? k_rx<1, kStageNarrow> : k_rx<1, kStageWide>)
+               : kind == 2 ? (tight ? k_rx<2, kStageTight> : narrow ? k_rx<2, kStageNarrow> : k_rx<2, kStageWide>)
+                           : (tight ? k_rx<0, kStageTight> : narrow ? k_rx<0, kStageNarrow> : k_rx<0, kStageWide>);
         e = emurx_launch(k, dim3(ntiles), dim3(kBlock), EMURX_RX_LDS_PAD, st, args);
     }
     if (!EMURX_HIP_OK(e)) return -1;

@@ -17,11 +17,6 @@ namespace emurx {
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
-// LDS bytes staged per wave (64 frames).  7 KiB keeps a workgroup's LDS under 32 KiB, so
-// five workgroups (20 waves) fit a CU; waves whose frames span more take the window path
-// LDS staging slab per wave (emurx_kernels.hip): two sizes, chosen per launch (kStageNarrow
-// gives 6 workgroups per CU instead of 5; waves wider than it take the window path)
-constexpr uint32_t kStageWide = 7168, kStageNarrow = 6144;
 
 // loads through the global address space (global_load_*): pointers rebuilt from integers or
 // kept in a struct would otherwise compile to flat loads, which also count on lgkmcnt and
@@ -1325,9 +1320,13 @@ __device__ __forceinline__ Probe probe_issue(const emurx_dev_tables& T, const Re
 
 // GetNs + the callback's client rule, given the two buckets.  `flow(cid)` gives the transport
 // flow decision of a tcp/udp frame whose client was found with the transport plugin.
-template <class Flow>
+// `dmac()` gives {k.dlo, k.dhi, k.mc6}, the destination MAC where IsUnicastToMe compares it and
+// the ICMPv6 source test (icmp and icmpv6 echo alone): a caller short of registers reads them
+// from the frame again there instead of holding the three words across the probes (k_rx's
+// tight slab, emurx_kernels.hip).
+template <class Flow, class Dmac>
 __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, const LKey& k, const Probe& p,
-                                             const Bucket& ce, Flow flow) {
+                                             const Bucket& ce, Flow flow, Dmac dmac) {
     const uint32_t cb = r.proto, plug = cb_plugin(cb);
     const uint32_t key = k.key, cbk = p.cbk, mlo = p.mlo, mhi = p.mhi;
     // ---- GetNs + ns.PluginCtx.Get(plugin) ----
@@ -1355,7 +1354,8 @@ __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, 
         if (cb == EMURX_CB_ARP) {
             client_result(r, h.cid, h.mhip >> 16, plug, true);
         } else {  // icmp: IsUnicastToMe against the MAC in the slot
-            const bool me = h.mlo == k.dlo && (h.mhip & 0xffffu) == k.dhi;
+            const uint3 dm = dmac();
+            const bool me = h.mlo == dm.x && (h.mhip & 0xffffu) == dm.y;
             client_result(r, me ? h.cid : EMURX_ID_NONE, 0, plug, false);
         }
         return;
@@ -1379,8 +1379,9 @@ __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, 
             clo = h.mlo;
             chi = h.mhip & 0xffffu;
         }
-        if (cid != EMURX_ID_NONE && !(clo == k.dlo && chi == k.dhi)) cid = EMURX_ID_NONE;
-        if (cid != EMURX_ID_NONE && k.mc6) cid = EMURX_ID_NONE;
+        const uint3 dm = dmac();
+        if (cid != EMURX_ID_NONE && !(clo == dm.x && chi == dm.y)) cid = EMURX_ID_NONE;
+        if (cid != EMURX_ID_NONE && dm.z) cid = EMURX_ID_NONE;
         client_result(r, cid, 0, plug, false);
         return;
     }
@@ -1399,6 +1400,12 @@ __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, 
     }
 }
 
+template <class Flow>
+__device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, const LKey& k, const Probe& p,
+                                             const Bucket& ce, Flow flow) {
+    resolve_done(T, r, k, p, ce, flow, [&]() { return make_uint3(k.dlo, k.dhi, k.mc6); });
+}
+
 // The same outcome as resolve_done with far fewer divergent branches (EMURX_FLATRES, build
 // variant for A/B): every table kind's answer from the first buckets by straight-line selects
 // (the client bucket read as MAC, IPv4 and IPv6 slots at once: the lane's key kind picks one),
@@ -1411,9 +1418,9 @@ __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, 
 #define EMURX_FLATRES 0
 #endif
 __device__ __forceinline__ bool any_lane(bool c) { return __ballot(c) != 0; }
-template <class Flow>
+template <class Flow, class Dmac>
 __device__ __forceinline__ void resolve_done_flat(const emurx_dev_tables& T, Rec& r, const LKey& k, const Probe& p,
-                                                  const Bucket& ce, Flow flow) {
+                                                  const Bucket& ce, Flow flow, Dmac dmac) {
     const uint32_t cb = r.proto, plug = cb_plugin(cb), key = k.key;
     const uint32_t w0 = r.vport, w1 = r.vlan0, w2 = r.vlan1;
     // ---- first buckets, every view at once ----
@@ -1472,7 +1479,8 @@ __device__ __forceinline__ void resolve_done_flat(const emurx_dev_tables& T, Rec
     if (isIp4) { cid = i4.cid; cpl = i4.mhip >> 16; clo = i4.mlo; chi = i4.mhip & 0xffffu; }
     if (isIp6) { cid = i6.cid; clo = i6.mlo; chi = i6.mhip & 0xffffu; }
     const bool icmp4 = isIp4 && cb != EMURX_CB_ARP;
-    if (icmp4 && !(clo == k.dlo && chi == k.dhi)) cid = EMURX_ID_NONE;  // IsUnicastToMe
+    const uint3 dm = dmac();
+    if (icmp4 && !(clo == dm.x && chi == dm.y)) cid = EMURX_ID_NONE;  // IsUnicastToMe
     check = !(icmp4 || key == kEui || isIp6);
     const bool ns_ok = ns != EMURX_ID_NONE && (nsr.y & (1u << plug));
     // GetFirstClient (dhcpsrv / eapol) and the EUI-64 RA-prefix check read client info
@@ -1487,7 +1495,7 @@ __device__ __forceinline__ void resolve_done_flat(const emurx_dev_tables& T, Rec
                 cid = EMURX_ID_NONE;
         }
     }
-    if ((key == kEui || isIp6) && cid != EMURX_ID_NONE && (!(clo == k.dlo && chi == k.dhi) || k.mc6)) cid = EMURX_ID_NONE;
+    if ((key == kEui || isIp6) && cid != EMURX_ID_NONE && (!(clo == dm.x && chi == dm.y) || dm.z)) cid = EMURX_ID_NONE;
     // ---- the outcome ----
     uint32_t lk = cid == EMURX_ID_NONE ? EMURX_LK_NO_CLIENT
                   : (check && !(cpl & (1u << plug))) ? EMURX_LK_CLIENT_NO_PLUGIN : EMURX_LK_CLIENT;
@@ -1506,22 +1514,26 @@ __device__ __forceinline__ void resolve_done_flat(const emurx_dev_tables& T, Rec
 }
 
 // GetNs + the callback's client rule against the tables (both bucket reads in flight together)
-template <class Flow>
-__device__ __forceinline__ void resolve(const emurx_dev_tables& T, Rec& r, const LKey& k, Flow flow) {
+template <class Flow, class Dmac>
+__device__ __forceinline__ void resolve(const emurx_dev_tables& T, Rec& r, const LKey& k, Flow flow, Dmac dmac) {
     const Probe p = probe_issue(T, r, k);
     Bucket ce{};
     if (p.ctab) ce = ld_bucket(p.ctab, p.cbk);
 #if EMURX_FLATRES == 2
     // hybrid: a wave whose lanes share one key kind takes the switch without divergence
     if (__ballot(k.key != (uint32_t)__builtin_amdgcn_readfirstlane((int)k.key)) == 0)
-        resolve_done(T, r, k, p, ce, flow);
+        resolve_done(T, r, k, p, ce, flow, dmac);
     else
-        resolve_done_flat(T, r, k, p, ce, flow);
+        resolve_done_flat(T, r, k, p, ce, flow, dmac);
 #elif EMURX_FLATRES
-    resolve_done_flat(T, r, k, p, ce, flow);
+    resolve_done_flat(T, r, k, p, ce, flow, dmac);
 #else
-    resolve_done(T, r, k, p, ce, flow);
+    resolve_done(T, r, k, p, ce, flow, dmac);
 #endif
+}
+template <class Flow>
+__device__ __forceinline__ void resolve(const emurx_dev_tables& T, Rec& r, const LKey& k, Flow flow) {
+    resolve(T, r, k, flow, [&]() { return make_uint3(k.dlo, k.dhi, k.mc6); });
 }
 
 // parse state -> Namespace / Client ids, lookup outcome, flow decision (replicated tables:
