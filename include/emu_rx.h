@@ -668,6 +668,86 @@ int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_des
                             uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
                             uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
 
+/* ---- ARP and ND cache learning, folded per batch ------------------------------------------
+   The ARP handler learns the sender of every request before it answers and of every unicast
+   reply (plugins/arp/arp.go:904-946 -> PluginArpNs.ArpLearn :886-901); the ND handler learns a
+   solicitation's source (plugins/ipv6/nd.go:1611-1620) and an advertisement's target
+   (:1687-1776).  ArpFlowTable.ArpLearn (arp.go:435-451) and Ipv6NsCacheFlowTable.NdLearn
+   (nd.go:608-624) are idempotent after their second application (they write the MAC, then
+   MoveToComplete from Incomplete or Refresh and otherwise set touch = true), so a batch's learning
+   folds exactly into one event per distinct (ns, kind, ip, mac) with a frame count: applying each
+   event's learn call once, and once more if count > 1, in the order the events are written,
+   leaves the Go tables as frame-by-frame handling would.  emurx_learn_dev writes those events.
+   d_rec: the records emurx_classify_dev wrote for d_frames / d_desc.  A frame is considered only
+   if rec.status == EMURX_ST_OK and its descriptor is no hole (else EMURX_LRN_NONE); header offsets
+   that do not fit the frame (emurx_classify_dev writes none) give EMURX_LRN_HOST.
+     arp     with kinds & EMURX_LRNK_ARP, callback arp and lookup >= EMURX_LK_NS_LEVEL: the Namespace
+             exists and has the arp plugin (arp.go:956-969).  l3 < 14 or l3 + 28 > len -> HOST.
+             Operation p[l3+6:l3+8] 1 -> ARP_REQ, whatever the target resolves to (ArpLearn runs
+             before the client lookup, :915-918); 2 -> ARP_REPLY unless the Ethernet destination is
+             ff:ff:ff:ff:ff:ff (:936-941), then NONE; any other -> NONE.  The key is {rec.ns_id,
+             kind, p[l3+14:l3+18], p[l3+8:l3+14]} (:886-901); a sender IP of 0.0.0.0 is learned like
+             any other (the Go code has no test for it).
+     nd      with kinds & EMURX_LRNK_ND, callback icmpv6, lookup EMURX_LK_NS_LEVEL.  l3 < 14, l3 +
+             40 > l4 or l4 + 4 > len -> HOST, before the type byte is read; code p[l4+1] != 0 or a
+             type other than 135, 136 -> NONE.
+             Type 135: the checks of nd.go:1550-1609 exactly as emurx_respond_kinds_dev runs them
+             (above, up to "target unspecified or multicast"; the same device functions), its option
+             reading included: more than 8 option bytes -> HOST.  Then :1611-1620: the source is
+             net.IP.IsGlobalUnicast, an SLLA is present and the IPv6 table holds no client for the
+             source in this Namespace -> ND_NS with the key {ns, kind, source, SLLA}; else NONE.
+             Type 136 (:1687-1776): len - (l4 + 4) < 20 -> NONE.  The options p[l4+24:len]: none ->
+             NONE; exactly {2, 1, mac} -> the target MAC; any other 8 bytes or 1..7 bytes -> NONE;
+             more than 8 -> HOST.  Hop limit p[l3+7] != 255 -> NONE; override flag p[l4+4] & 0x20
+             clear -> NONE; a target p[l4+8:l4+24] neither link-local nor global -> NONE.  An EUI-64
+             target is learned unless the MAC table holds the extracted MAC with IsValidPrefix (the
+             responder's question, without the plugin test); any other target unless the IPv6 table
+             holds it (pktRxNeighborAdvWithOwnAddr).  The key is {ns, kind, target, target MAC}; a
+             zero target MAC is learned (the Go code checks it only for solicitations).
+             The net.IP predicates are those of the responder.
+   An event is the fold of all frames with one key: count frames, first / last the lowest and
+   highest rx frame index among them.  Events are written in ascending `last` (frame indices are
+   distinct, so the output is fully determined).  d_info (u64[EMURX_LRN_INFO_WORDS]) = {events
+   written, distinct keys, overflow (0 or 1), frames with outcome 1..5}.  Overflow is distinct
+   keys > ev_cap and nothing else: then d_info[0] is 0 and nothing is written to d_ev, while
+   d_outcome and d_info[1..7] stay valid (handle the batch's learning frames one by one, or call
+   again with a larger ev_cap).  Nothing is ever written at or past d_ev[ev_cap].
+   kinds == 0 or a bit above EMURX_LRNK_ALL, ev_cap == 0 or ev_cap > emurx_learn_max_events(h)
+   are EMURX_EINVAL; n > cfg.max_frames is EMURX_ENOMEM.  emurx_learn_max_events(h) is half the
+   slot count of the handle's set (a power of two >= 2 * max_frames, so a batch's keys always
+   fit it and a probe always ends at a free slot).  d_rec 16-byte aligned, d_desc, d_ev and d_info
+   8-byte; d_outcome [n] may be NULL.  n < EMURX_TX_ZMQ_MAX_FRAMES; n == 0 writes a zero d_info.
+   Four launches on `stream` (decide + fold, mark, scan, emit), no host synchronisation and no
+   allocation (the scratch is sized at emurx_open from max_frames), behind the table shipment
+   emurx_classify_dev describes; calls on different streams of one handle share the scratch, so
+   they must not overlap.  A frame the responder answered (outcome EMURX_RSP_ARP or EMURX_RSP_ND)
+   whose learn outcome is not EMURX_LRN_HOST needs no Go handler when the batch did not overflow:
+   INTEGRATION.md has the replay loop. */
+typedef struct emurx_learn_ev {
+    uint32_t ns_id;    /* rec.ns_id of the frames folded                                   */
+    uint32_t count;    /* frames folded into this event (>= 1)                             */
+    uint32_t first;    /* lowest rx frame index among them                                 */
+    uint32_t last;     /* highest; events are written in ascending `last`                  */
+    uint8_t  ip[16];   /* ARP: sender IPv4 in ip[0:4] (wire order), ip[4:16] zero; ND: IPv6 */
+    uint8_t  mac[6];
+    uint8_t  kind;     /* enum emurx_lrn 1..4                                              */
+    uint8_t  pad;      /* 0                                                                */
+} emurx_learn_ev;      /* 40 bytes */
+enum emurx_lrn {            /* per-frame outcome, d_outcome[i]; 1..4 are also the event kinds */
+    EMURX_LRN_NONE = 0,       /* nothing to learn from this frame */
+    EMURX_LRN_ARP_REQ = 1, EMURX_LRN_ARP_REPLY = 2, EMURX_LRN_ND_NS = 3, EMURX_LRN_ND_NA = 4,
+    EMURX_LRN_HOST = 5        /* the Go handler must decide (an option chain, offsets that do not fit) */
+};
+#define EMURX_LRNK_ARP 1u
+#define EMURX_LRNK_ND  2u
+#define EMURX_LRNK_ALL 3u
+#define EMURX_LRN_INFO_WORDS 8
+uint32_t emurx_learn_max_events(const emurx_t* h);
+int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                    const emurx_rec* d_rec, uint32_t n, uint32_t kinds,
+                    emurx_learn_ev* d_ev, uint32_t ev_cap,
+                    uint8_t* d_outcome, uint64_t* d_info, void* stream);
+
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);
 /* Sum the EMURX_HIST_SHARDS copies of a device histogram (after a D2H copy). */

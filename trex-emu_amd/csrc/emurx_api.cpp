@@ -192,6 +192,10 @@ struct emurx_ctx {
     int last_txz = -1;
     // the device responder's scratch (emurx_respond_dev): plans and tile sums, no state between calls
     DevBuf<uint8_t> d_rsp;
+    // the cache-learning fold's scratch (emurx_learn_dev), sized at emurx_open from max_frames: its
+    // set is zero between calls; a call whose launches failed half way leaves it to be cleared
+    DevBuf<uint8_t> d_lrn;
+    bool lrn_dirty = false;
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -849,6 +853,11 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
             return EMURX_EDEVICE;
         }
     memset(h->stage_fb.p, 0, 256 * sizeof(uint32_t));
+    if (h->d_lrn.alloc(emurx_lrn_scratch_bytes(cfg->max_frames)) ||
+        !EMURX_HIP_OK(hipMemset(h->d_lrn.p, 0, (size_t)emurx_lrn_slots(cfg->max_frames) * 16))) {
+        emurx_close(h);
+        return EMURX_ENOMEM;
+    }
     emurx_t::RouteScratch* rs = nullptr;
     if ((rc = ship_tables(h, h->stream)) || (rc = route_scratch(h, cfg->max_frames, h->stream, &rs)) == EMURX_ENOMEM) {
         emurx_close(h);
@@ -883,6 +892,7 @@ void emurx_close(emurx_t* h) {
     for (auto& r : h->route) r.release();
     h->d_txz.release();
     h->d_rsp.release();
+    h->d_lrn.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
     for (auto& e : h->ev)
@@ -1423,6 +1433,37 @@ int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_des
                             uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
     return respond_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSP_INFO_WORDS, d_out, out_cap, d_out_desc, d_out_src,
                          d_outcome, d_info, stream);
+}
+
+uint32_t emurx_learn_max_events(const emurx_t* h) { return h ? emurx_lrn_slots(h->cfg.max_frames) / 2 : 0; }
+
+int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                    uint32_t kinds, emurx_learn_ev* d_ev, uint32_t ev_cap, uint8_t* d_outcome, uint64_t* d_info,
+                    void* stream) {
+    if (!h || !d_info || !d_ev || (n && (!d_frames || !d_desc || !d_rec))) return EMURX_EINVAL;
+    if (kinds == 0 || (kinds & ~EMURX_LRNK_ALL)) return EMURX_EINVAL;
+    if (ev_cap == 0 || ev_cap > emurx_learn_max_events(h)) return EMURX_EINVAL;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ev & 7) ||
+        ((uintptr_t)d_info & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;  // the scratch is sized at emurx_open
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // a solicitation's source and an advertisement's target are looked up in the MAC, IPv6 and
+    // client-info tables: behind the shipment of pending edits, like a classify
+    if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
+    if (h->lrn_dirty) {
+        if (!EMURX_HIP_OK(hipMemsetAsync(h->d_lrn.p, 0, (size_t)emurx_lrn_slots(h->cfg.max_frames) * 16, st)))
+            return EMURX_EDEVICE;
+        h->lrn_dirty = false;
+    }
+    if (emurx_launch_learn(d_frames, d_desc, d_rec, n, kinds, h->tables(), d_ev, ev_cap, d_outcome, d_info, h->d_lrn.p,
+                           h->cfg.max_frames, st)) {
+        h->lrn_dirty = true;
+        return EMURX_EDEVICE;
+    }
+    return EMURX_OK;
 }
 
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {

@@ -162,6 +162,15 @@ int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const em
                          uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, void* scratch,
                          hipStream_t st);
 
+// The cache-learning fold (emurx_learn.hip): see emurx_learn_dev.  scratch:
+// emurx_lrn_scratch_bytes(max_frames), whose first emurx_lrn_slots(max_frames) * 16 bytes (the
+// set) are zero before the first call; every call leaves them zero.  n <= max_frames.  Four launches.
+uint32_t emurx_lrn_slots(uint32_t max_frames);
+size_t emurx_lrn_scratch_bytes(uint32_t max_frames);
+int emurx_launch_learn(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n, uint32_t kinds,
+                       const emurx_dev_tables& T, emurx_learn_ev* ev, uint32_t ev_cap, uint8_t* outcome, uint64_t* info,
+                       void* scratch, uint32_t max_frames, hipStream_t st);
+
 // Tx ZMQ framing (emurx_txzmq.hip): see emurx_tx_zmq_dev.  scratch: emurx_txz_scratch_bytes(n).
 size_t emurx_txz_scratch_bytes(uint32_t n);
 // variant: the write kernel's image (EMURX_TXZ_*, emurx_tx_zmq_dev's feedback choice); feedback:

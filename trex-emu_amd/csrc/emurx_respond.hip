@@ -30,6 +30,7 @@
 #include "../../include/emu_rx.h"
 #include "emurx_kernels.h"
 #include "emurx_parse.h"
+#include "emurx_rsp_dev.h"
 
 namespace emurx {
 
@@ -58,10 +59,6 @@ __device__ __forceinline__ bool rsp_ip4_src_ok(uint32_t ip) {
     return !(ip == 0 || ip == 0xffffffffu || (b0 & 0xf0) == 0xe0 || (b0 == 169 && b1 == 254));
 }
 
-__device__ __forceinline__ uint32_t rsp_le32(const uint8_t* p) {  // any alignment
-    return gld1(p) | gld1(p + 1) << 8 | gld1(p + 2) << 16 | gld1(p + 3) << 24;
-}
-
 // the client of (record's tunnel key, ip) in the IPv4 table, with its MAC (CLookupByIPv4)
 __device__ __forceinline__ IpHit rsp_probe_ip4(const emurx_dev_tables& T, uint32_t ns, uint32_t vport, uint32_t v0,
                                                uint32_t v1, uint32_t ip) {
@@ -84,7 +81,6 @@ __device__ __forceinline__ bool rsp_candidate(const uint4& b, uint32_t kinds) {
 __device__ __forceinline__ bool rsp_is_reply(uint32_t outcome) {
     return (outcome >= EMURX_RSP_ARP && outcome <= EMURX_RSP_ICMPV6) || outcome == EMURX_RSP_ND;
 }
-__device__ __forceinline__ void rsp_load16(uintptr_t F, uint32_t flen, int s, uint32_t o[4]);
 
 // The decision for a candidate frame.  Header offsets that do not fit the frame (no record of
 // emurx_classify_dev for these descriptors has them) give EMURX_RSP_HOST: never guess.
@@ -121,33 +117,6 @@ __device__ RspPlan rsp_decide(const uint8_t* __restrict__ frames, const emurx_de
     return {EMURX_RSP_ICMPV6, len - strip};
 }
 
-// The client that answers a solicitation for target t (words LE), and its MAC (nd.go:1626-1678).
-// EUI-64 target: CLookupByMac of the extracted MAC + IsValidPrefix (client_ctx.go:279-295);
-// otherwise, a global target: CLookupByIPv6.  Then the client's ipv6 plugin.
-struct RspNdHit {
-    bool ok;
-    uint32_t mlo, mhi;
-};
-__device__ __forceinline__ bool rsp_nd_eui(const uint32_t t[4]) { return (t[2] >> 24) == 0xffu && (t[3] & 0xffu) == 0xfeu; }
-__device__ __forceinline__ RspNdHit rsp_nd_ip6(const emurx_dev_tables& T, uint32_t ns, uint32_t tk, const uint32_t t[4]) {
-    const uint32_t bk = emurx_ip6_hash(tk, t[0], t[1], t[2], t[3]) & T.ip6_mask;
-    const IpHit h = resolve_ip6(T, bk, ld_bucket(T.ip6_tab, bk), ns, t);
-    return {h.cid != EMURX_ID_NONE && ((h.mhip >> 16) & (1u << EMURX_PLUG_IPV6)), h.mlo, h.mhip & 0xffffu};
-}
-__device__ RspNdHit rsp_nd_client(const emurx_dev_tables& T, uint32_t ns, uint32_t tk, const uint32_t t[4], bool global) {
-    if (!rsp_nd_eui(t)) return global ? rsp_nd_ip6(T, ns, tk, t) : RspNdHit{false, 0, 0};
-    const uint2 m = eui_mac(t[2], t[3]);
-    if (m.x == 0 && m.y == 0) return {false, 0, 0};  // MACKey.IsZero never matches
-    const uint32_t bk = emurx_mac_hash(tk, m.x, m.y) & T.mac_mask;
-    const uint2 c = resolve_mac(T, bk, ld_bucket(T.mac_tab, bk), ns, m.x, m.y);
-    if (c.x == EMURX_ID_NONE) return {false, 0, 0};
-    if (!(t[0] == 0x000080feu && t[1] == 0)) {  // not fe80::/64: the client's RA prefix, length 64
-        const CInfo ci = client_info(T, c.x);
-        if (!((ci.ra & 1u) && ((ci.ra >> 8) & 0xff) == 64 && ci.ra0 == t[0] && ci.ra1 == t[1])) return {false, 0, 0};
-    }
-    return {(c.y & (1u << EMURX_PLUG_IPV6)) != 0, m.x, m.y};
-}
-
 // The decision for a neighbour solicitation candidate (nd.go:1546-1685; the rule with its
 // citations is in include/emu_rx.h).  A reply if and only if the Go handler would reach
 // nd.Respond; HOST where a lane cannot cheaply decide.
@@ -158,33 +127,15 @@ __device__ RspPlan rsp_decide_nd(const uint8_t* __restrict__ frames, const emurx
     if (d.pad == EMURX_DESC_HOLE) return {EMURX_RSP_NONE, 0};
     if (l3 < 14 || l3 + 40 > l4 || l4 + 4 > len) return {EMURX_RSP_HOST, 0};
     if (gld1(f + l4) != 135 || gld1(f + l4 + 1) != 0) return {EMURX_RSP_NONE, 0};
-    if (len - (l4 + 4) < 20) return {EMURX_RSP_NONE, 0};  // pktRxErrTooShort
-    // the options are the rest of the frame: none, or one source link-layer address
-    const uint32_t nopt = len - (l4 + 24);
-    if (nopt > 8) return {EMURX_RSP_HOST, 0};
-    if (nopt != 0 && nopt != 8) return {EMURX_RSP_NONE, 0};
-    const uintptr_t F = (uintptr_t)f;
-    uint32_t w[4];
-    const bool slla = nopt == 8;
-    if (slla) {
-        rsp_load16(F, len, (int)(l4 + 24), w);  // w[0], w[1]: the option
-        if ((w[0] & 0xffffu) != 0x0101u) return {EMURX_RSP_NONE, 0};
-        if ((w[0] >> 16) == 0 && w[1] == 0) return {EMURX_RSP_NONE, 0};
-    }
-    if (gld1(f + l3 + 7) != 255) return {EMURX_RSP_NONE, 0};
-    rsp_load16(F, len, (int)(l3 + 8), w);  // the source
-    if (ip6_unspecified(w)) {
-        if (slla) return {EMURX_RSP_NONE, 0};
-        rsp_load16(F, len, (int)(l3 + 24), w);  // the destination
-        if (!ip6_multicast(w)) return {EMURX_RSP_NONE, 0};
-    }
-    rsp_load16(F, len, (int)(l4 + 8), w);  // the target
-    if (ip6_unspecified(w) || ip6_multicast(w)) return {EMURX_RSP_NONE, 0};
-    const bool global = ip6_global(w);
-    if (!(ip6_link_local(w) || global)) return {EMURX_RSP_NONE, 0};
-    const uint32_t tk = emurx_tk_hash(b.x & 0xffffu, a.z, a.w);
-    if (!rsp_nd_client(T, a.x, tk, w, global).ok) return {EMURX_RSP_NONE, 0};
-    return {EMURX_RSP_ND, 86u + 4u * ((a.z != 0) + (a.w != 0))};
+    return rsp_nd_checks(  // emurx_rsp_dev.h
+        f, l3, l4, len, [](uint32_t o) { return RspPlan{o, 0}; },
+        [&](const uint32_t(&w)[4], bool, uint2, const uint32_t(&)[4]) -> RspPlan {
+            const bool global = ip6_global(w);
+            if (!(ip6_link_local(w) || global)) return {EMURX_RSP_NONE, 0};
+            const uint32_t tk = emurx_tk_hash(b.x & 0xffffu, a.z, a.w);
+            if (!rsp_nd_client(T, a.x, tk, w, global).ok) return {EMURX_RSP_NONE, 0};
+            return {EMURX_RSP_ND, 86u + 4u * ((a.z != 0) + (a.w != 0))};
+        });
 }
 
 // tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows.
@@ -301,23 +252,6 @@ __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restr
     }
 }
 
-// E[s .. s + 16) of the frame E = [F, F + flen), s of either sign, as four little-endian words:
-// the two aligned 16-byte blocks that hold the span, read only where they hold a byte of the
-// frame (zeros elsewhere: the caller masks those bytes out), funnel-shifted
-__device__ __forceinline__ void rsp_load16(uintptr_t F, uint32_t flen, int s, uint32_t o[4]) {
-    const uintptr_t a = F + (intptr_t)s, A = a & ~(uintptr_t)15, Fend = F + flen;
-    const uint32_t sh = (uint32_t)(a & 15), q = sh >> 2, bsh = sh & 3;
-    uint4 x = make_uint4(0, 0, 0, 0), y = x;
-    if (A < Fend && A + 16 > F) x = gld16(reinterpret_cast<const void*>(A));
-    if (sh && A + 16 < Fend && A + 32 > F) y = gld16(reinterpret_cast<const void*>(A + 16));
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = q == 0 ? w[i] : q == 1 ? w[i + 1] : q == 2 ? w[i + 2] : w[i + 3];
-        const uint32_t hi = q == 0 ? w[i + 1] : q == 1 ? w[i + 2] : q == 2 ? w[i + 3] : w[i + 4];
-        o[i] = __builtin_amdgcn_alignbyte(hi, lo, bsh);
-    }
-}
 // the mask of the bytes [lo, hi) of a row (0 <= lo < hi <= 16) that lie in its dword d
 __device__ __forceinline__ uint32_t rsp_bytes(int lo, int hi, int d) {
     const int a = max(lo - 4 * d, 0), b = min(hi - 4 * d, 4);

@@ -117,6 +117,15 @@ RSP_ND = 7  # neighbour advertisement written (emurx_respond_kinds_dev with RSPK
 # EMURX_RSPK_*: the answers emurx_respond_kinds_dev is asked for; its d_info has RSP_INFO_WORDS words
 RSPK_ARP, RSPK_ICMP, RSPK_ICMPV6, RSPK_ND, RSPK_ALL = 1, 2, 4, 8, 15
 RSP_INFO_WORDS = 16
+# enum emurx_lrn: the per-frame outcome of emurx_learn_dev; 1..4 are also the kinds of its events
+LRN_NONE, LRN_ARP_REQ, LRN_ARP_REPLY, LRN_ND_NS, LRN_ND_NA, LRN_HOST = range(6)
+# EMURX_LRNK_*: the learning emurx_learn_dev is asked to fold; its d_info has LRN_INFO_WORDS words
+LRNK_ARP, LRNK_ND, LRNK_ALL = 1, 2, 3
+LRN_INFO_WORDS = 8
+# emurx_learn_ev: one event per distinct (ns, kind, ip, mac) of a batch
+LEARN_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("count", "<u4"), ("first", "<u4"), ("last", "<u4"), ("ip", "u1", 16),
+                           ("mac", "u1", 6), ("kind", "u1"), ("pad", "u1")])
+assert LEARN_EV_DTYPE.itemsize == 40
 FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xFFFFFFF0, 0xFFFFFFF1,
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
@@ -229,6 +238,8 @@ SIGNATURES = [
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("emurx_learn_max_events", C.c_uint32, [_P]),
+    ("emurx_learn_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -278,8 +289,8 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
-           "emurx_respond.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
-    hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_parse.h", "emurx_mirror.h"]
+           "emurx_respond.hip", "emurx_learn.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+    hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()
     try:

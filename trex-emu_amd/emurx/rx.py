@@ -275,6 +275,20 @@ class RxPath:
                                                           _addr(out), cap, _addr(out_desc), _addr(out_src), _addr(outcome),
                                                           _addr(info), _stream(stream)), "respond_kinds_dev")
 
+    def learn_max_events(self) -> int:
+        """The largest ev_cap learn_dev takes: half the slot count of the handle's set."""
+        return int(self.lib.emurx_learn_max_events(self.h))
+
+    def learn_dev(self, frames, desc, rec, n: int, ev, ev_cap: int, outcome, info, kinds: int = abi.LRNK_ALL,
+                  stream=None):
+        """The ARP / ND cache learning of a classified batch folded on the device into one event
+        per distinct (ns, kind, ip, mac) (include/emu_rx.h emurx_learn_dev): ev
+        abi.LEARN_EV_DTYPE [ev_cap], written in ascending `last`; outcome u8 [n] (abi.LRN_*, or
+        None); info u64[abi.LRN_INFO_WORDS] {events written, distinct keys, overflow, frames per
+        outcome 1..5}.  On overflow (distinct keys > ev_cap) no event is written."""
+        return abi.check(self.lib.emurx_learn_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds, _addr(ev),
+                                                  ev_cap, _addr(outcome), _addr(info), _stream(stream)), "learn_dev")
+
     # ---- Namespace-partitioned exchange ---------------------------------------------------
     def classify_route_dev(self, frames, desc, n: int, rec, qlist, qcap: int, tile_cnt, hist, n_parts: int,
                            my_rank: int, cap: int, send, send_count, stream=None, flow=None):
