@@ -375,6 +375,13 @@ int emurx_recs_stale(const emurx_t* h, const emurx_rec* rec, uint32_t n, uint64_
    6 flow6 {client, src[4], dst[4], ports, nh} -> flow, 7 listener {client, port | proto << 16} -> 1
    (words little-endian as in the tables).  EMURX_ENOENT when absent. */
 int emurx_image_lookup(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t* value);
+/* The same walk with its trace (tests that need keys at chosen places of a table: long chains,
+   the step across the table's end, tombstones).  Tables, key words and return codes as
+   emurx_image_lookup.  out[0] the value (EMURX_ID_NONE when absent), out[1] the table's bucket
+   count, out[2] the key's home bucket, out[3] buckets the walk read, out[4] 1 if it stepped
+   from the last bucket to bucket 0, out[5] tombstone slots it passed.  A mac / ipv4 / ipv6 key
+   whose Namespace is not alive reads no bucket: EMURX_ENOENT, out all zero. */
+int emurx_image_probe(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t out[6]);
 /* Compare the device tables with the host image after a shipment (synchronises the handle's
    stream): *mismatched = 32-bit words that differ. */
 int emurx_image_check(emurx_t* h, uint64_t* mismatched);

@@ -27,7 +27,8 @@ GROUPS = [
     ("Transport tables", ["emurx_flow_add", "emurx_flow_remove", "emurx_server_add", "emurx_server_remove",
                           "emurx_client_set_transport"],
      "`TransportCtx` maps `transport/client_ctx.go:490-497`"),
-    ("Table shipment and diagnostics", ["emurx_sync", "emurx_table_stats", "emurx_image_lookup", "emurx_image_check"],
+    ("Table shipment and diagnostics", ["emurx_sync", "emurx_table_stats", "emurx_image_lookup", "emurx_image_probe",
+                                        "emurx_image_check"],
      "(device image of the maps above)"),
     ("Mid-batch mutations", ["emurx_table_gen", "emurx_recs_stale"], "DESIGN.md §2.2, `dhcp.go:718`"),
     ("Batched ingest (primary)", ["emurx_ingest_buffer", "emurx_ingest_submit", "emurx_ingest_wait",
@@ -51,6 +52,8 @@ GROUPS = [
     ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev"],
      "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`, "
      "`NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
+    ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events"],
+     "`PluginArpNs.ArpLearn` `arp/arp.go:886-901`, `NdLearn` `ipv6/nd.go:1611-1620`, `:1687-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

@@ -1029,6 +1029,10 @@ int emurx_image_lookup(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t
     if (!h) return EMURX_EINVAL;
     return h->m.image_lookup(table, key, value);
 }
+int emurx_image_probe(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t out[6]) {
+    if (!h) return EMURX_EINVAL;
+    return h->m.image_probe(table, key, out);
+}
 int emurx_image_check(emurx_t* h, uint64_t* mismatched) {
     using namespace emurx_host;
     if (!h || !mismatched) return EMURX_EINVAL;

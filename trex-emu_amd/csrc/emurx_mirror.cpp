@@ -622,7 +622,17 @@ bool Mirror::stale(const emurx_rec& r, uint64_t since) const {
 
 // ---- the device walk over the host image (tests of the table maintenance) -------------------
 int Mirror::image_lookup(uint32_t table, const uint32_t* key, uint32_t* value) {
-    if (table >= kNumTabs || !key || !value) return EMURX_EINVAL;
+    if (!value) return EMURX_EINVAL;
+    uint32_t out[6];
+    const int rc = image_probe(table, key, out);
+    if (rc == EMURX_OK) *value = out[0];
+    return rc;
+}
+
+// the one host walk: image_lookup's answer is out[0]
+int Mirror::image_probe(uint32_t table, const uint32_t* key, uint32_t out[6]) {
+    if (table >= kNumTabs || !key || !out) return EMURX_EINVAL;
+    memset(out, 0, 6 * sizeof(uint32_t));
     Hash& t = *hashes((int)table);
     uint32_t h = 0, nk = 0;
     uint32_t kw[11] = {0};
@@ -645,13 +655,18 @@ int Mirror::image_lookup(uint32_t table, const uint32_t* key, uint32_t* value) {
     case kTabSrv: h = emurx_srv_hash(key[0], key[1]); nk = 2; break;
     }
     memcpy(kw, key, nk * 4);
+    out[0] = EMURX_ID_NONE;
+    out[1] = t.buckets;
+    out[2] = h & t.mask();
     for (uint32_t b = h & t.mask(), n = 0; n < t.buckets; b = (b + 1) & t.mask(), ++n) {
         bool hole = false;
+        ++out[3];
+        if (n && b == 0) out[4] = 1;
         for (uint32_t k = 0; k < t.per(); ++k) {
             const uint32_t* s = &t.img[(size_t)b * EMURX_BUCKET_WORDS + k * t.words];
             const uint32_t v = s[t.words - 1];
             if (v == EMURX_EMPTY) { hole = true; continue; }
-            if (v == EMURX_TOMB) continue;
+            if (v == EMURX_TOMB) { ++out[5]; continue; }
             bool eq = true;
             for (uint32_t j = 0; j < nk && eq; ++j) {
                 uint32_t x = s[j];
@@ -659,7 +674,7 @@ int Mirror::image_lookup(uint32_t table, const uint32_t* key, uint32_t* value) {
                 eq = x == kw[j];
             }
             if (eq) {
-                *value = table == kTabCi ? s[1] : v;  // client info: its plugin mask
+                out[0] = table == kTabCi ? s[1] : v;  // client info: its plugin mask
                 return EMURX_OK;
             }
         }

@@ -170,6 +170,9 @@ struct Mirror {
     bool stale(const emurx_rec& r, uint64_t since) const;
     // the device image's answer for a key (the kernels' bucket walk over the host image)
     int image_lookup(uint32_t table, const uint32_t* key, uint32_t* value);
+    // that walk with its trace: out = {value or EMURX_ID_NONE, buckets, home bucket, buckets read,
+    // stepped from the last bucket to bucket 0, tombstone slots passed} (emu_rx.h emurx_image_probe)
+    int image_probe(uint32_t table, const uint32_t* key, uint32_t out[6]);
 
    private:
     uint32_t tk_of(uint32_t ns_id) const;

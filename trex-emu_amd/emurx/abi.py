@@ -228,6 +228,7 @@ SIGNATURES = [
     ("emurx_table_gen", C.c_uint64, [_P]),
     ("emurx_recs_stale", C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P]),
     ("emurx_image_lookup", C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    ("emurx_image_probe", C.c_int, [_P, C.c_uint32, _P, _P]),
     ("emurx_image_check", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("emurx_table_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("emurx_ingest_buffer", C.c_int, [_P, C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p)]),

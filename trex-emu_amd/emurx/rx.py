@@ -410,6 +410,18 @@ class RxPath:
         abi.check(rc, "image_lookup")
         return v.value
 
+    def image_probe(self, table: int, key) -> dict:
+        """emurx_image_probe: image_lookup's walk with its trace.  value None when absent;
+        buckets 0 where the walk read nothing (a client key of a dead Namespace)."""
+        k = np.ascontiguousarray(key, dtype=np.uint32)
+        out = np.zeros(6, np.uint32)
+        rc = self.lib.emurx_image_probe(self.h, table, _p(k), _p(out))
+        if rc != abi.EMURX_ENOENT:
+            abi.check(rc, "image_probe")
+        v, nb, home, reads, wrapped, tombs = (int(x) for x in out)
+        return dict(value=None if rc == abi.EMURX_ENOENT else v, buckets=nb, home=home, reads=reads,
+                    wrapped=bool(wrapped), tombstones=tombs)
+
     def image_check(self) -> int:
         """32-bit words where the device tables differ from the host image (0 = in sync)."""
         v = C.c_uint64()
