@@ -782,6 +782,21 @@ const char* emurx_build_id(void);
    forces one.  Results never depend on it.  No ABI replacement: a tuning
    observable of this implementation. */
 uint32_t emurx_last_stage(const emurx_t* h);
+/* Which of the sampled waves of the most recent k_rx launch took the uniform-wave path: a staged
+   wave whose 64 frames share one plain shape (the same number of 802.1Q tags, IPv4 without
+   options or fragments, all UDP or all TCP, each exactly as long as its total length says) is
+   parsed by straight-line code, and in a classifying launch its lookups are too when every
+   frame reached the plain udp / tcp callback and hit the first slot of its home buckets.  Any
+   other wave runs the general code; results never depend on the path.  The waves of every 64th
+   tile are sampled: words[(tile / 64 % 64) * 4 + wave] is EMURX_UNI_SAMPLED, or-ed with
+   EMURX_UNI_PARSE and EMURX_UNI_LOOKUP for the parts that took the path; 0 for a wave the
+   launch did not sample.  Waits for the device.  EMURX_UNIFORM=0 in the environment at emurx_open
+   switches the path off (default on).  A tuning observable, no ABI replacement. */
+#define EMURX_UNI_WORDS 256
+#define EMURX_UNI_PARSE 1u
+#define EMURX_UNI_LOOKUP 2u
+#define EMURX_UNI_SAMPLED 4u
+int emurx_last_uniform(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]);
 /* LDS image (bytes per wave) of the most recent tx framing write (emurx_tx_zmq_dev): 6144,
    4608 or 0 (every tile on the rows-over-lanes path); -1 before the first.  Chosen per call from
    the tile sizes an earlier call's chain kernel saw; EMURX_TXZ=wide|narrow|long at emurx_open

@@ -55,7 +55,7 @@ GROUPS = [
     ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events"],
      "`PluginArpNs.ArpLearn` `arp/arp.go:886-901`, `NdLearn` `ipv6/nd.go:1611-1620`, `:1687-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
-                     "emurx_last_txz"],
+                     "emurx_last_uniform", "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),
 ]
 

@@ -229,7 +229,11 @@ struct emurx_ctx {
     // decision in a row that sees it eligible, the first of which chose narrow: one sample is
     // too little evidence.  Any decision that sees more than 1 % of the waves over 5 KiB leaves
     // it at once.  EMURX_STAGE=wide|narrow|tight forces one size (tests, A/B).
+    // The same sampled waves write a second word each behind the first 256, {gen << 2, lookups
+    // uniform << 1, parse uniform}: which of them took the uniform-wave path (emurx_parse.h).
+    // EMURX_UNIFORM=0 switches that path off (default on); emurx_last_uniform reads the words
     DevBuf<uint32_t> d_stage_fb;  // 64 sampled tiles x 4 waves: gen << 3 | over_5k << 2 | has_frames << 1 | mid
+    bool uniform = true;
     PinBuf<uint32_t> stage_fb;    // its copy
     uint32_t stage_gen = 0, stage_mode = 0;  // 0 auto, 1 wide, 2 narrow, 3 tight
     bool stage_copy = false, stage_pending = false;
@@ -524,7 +528,7 @@ int run_dev(emurx_t* h, const uint8_t* frames, const emurx_desc* desc, uint32_t 
         h->ev_count = std::min(h->ev_count + 1, h->slots);
     }
     const uint32_t stage = choose_stage(h);
-    int r = emurx_launch_batch(frames, desc, n, T, kind, *out, st, ev, stage, h->d_stage_fb.p, h->stage_gen, rt);
+    int r = emurx_launch_batch(frames, desc, n, T, kind, *out, st, ev, stage, h->d_stage_fb.p, h->stage_gen, h->uniform, rt);
     if (!r) r = stage_copy_back(h, st);
     return r ? EMURX_EDEVICE : EMURX_OK;
 }
@@ -686,7 +690,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
         const emurx_dev_out o{s.d_rec.p, s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, s.d_hist.p};
         const uint32_t stage = choose_stage(h);
         if (emurx_launch_batch(s.d_buf.p, s.d_desc.p, n, h->tables(), true, o, st, nullptr, stage,
-                               h->d_stage_fb.p, h->stage_gen) ||
+                               h->d_stage_fb.p, h->stage_gen, h->uniform) ||
             stage_copy_back(h, st))
             return EMURX_EDEVICE;
     }
@@ -826,6 +830,7 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
     if (rc) { delete h; return rc; }
     if (!EMURX_HIP_OK(hipStreamCreate(&h->stream))) { delete h; return EMURX_EDEVICE; }
     if (const char* e = getenv("EMURX_STAGE")) h->stage_mode = !strcmp(e, "wide") ? 1 : !strcmp(e, "narrow") ? 2 : !strcmp(e, "tight") ? 3 : 0;
+    if (const char* e = getenv("EMURX_UNIFORM")) h->uniform = strcmp(e, "0") != 0;
     if (const char* e = getenv("EMURX_INGEST_SMALL")) h->ingest_small = strcmp(e, "0") != 0;
     if (const char* e = getenv("EMURX_TXZ"))
         h->txz_mode = !strcmp(e, "wide") ? EMURX_TXZ_WIDE : !strcmp(e, "narrow") ? EMURX_TXZ_NARROW
@@ -840,10 +845,10 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
         const uint32_t cap = emurx_ingest_small_capacity(cfg->device);
         h->small_tiles = std::min<uint32_t>(EMURX_SMALL_TILES, cap);
     }
-    if (h->stage_fb.alloc(256) || h->d_stage_fb.alloc(256) ||
+    if (h->stage_fb.alloc(256) || h->d_stage_fb.alloc(2 * emurx::kFbWords) ||
         !EMURX_HIP_OK(hipEventCreateWithFlags(&h->stage_ev, hipEventDisableTiming)) ||
         !EMURX_HIP_OK(hipEventCreateWithFlags(&h->ship_ev, hipEventDisableTiming)) ||
-        !EMURX_HIP_OK(hipMemset(h->d_stage_fb.p, 0, 256 * sizeof(uint32_t)))) {
+        !EMURX_HIP_OK(hipMemset(h->d_stage_fb.p, 0, 2 * emurx::kFbWords * sizeof(uint32_t)))) {
         emurx_close(h);
         return EMURX_ENOMEM;
     }
@@ -1309,6 +1314,18 @@ int emurx_set_timing(emurx_t* h, uint32_t slots, uint32_t stride) {
 }
 
 uint32_t emurx_last_stage(const emurx_t* h) { return h ? h->last_stage : 0; }
+int emurx_last_uniform(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]) {
+    static_assert(EMURX_UNI_WORDS == emurx::kFbWords, "one path word per sampled wave");
+    if (!h || !words) return EMURX_EINVAL;
+    if (bind(h)) return EMURX_EDEVICE;  // a host-only handle launches nothing
+    if (!EMURX_HIP_OK(hipDeviceSynchronize()) ||
+        !EMURX_HIP_OK(hipMemcpy(words, h->d_stage_fb.p + emurx::kFbWords, EMURX_UNI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost)))
+        return EMURX_EDEVICE;
+    // the words of the most recent launch alone (k_rx tags them with its generation)
+    for (uint32_t i = 0; i < EMURX_UNI_WORDS; ++i)
+        words[i] = h->stage_gen && (words[i] >> 2) == h->stage_gen ? EMURX_UNI_SAMPLED | (words[i] & 3u) : 0u;
+    return EMURX_OK;
+}
 int32_t emurx_last_txz(const emurx_t* h) {
     if (!h || h->last_txz < 0) return -1;
     return h->last_txz == EMURX_TXZ_NARROW ? 4608 : h->last_txz == EMURX_TXZ_LONG ? 0 : 6144;

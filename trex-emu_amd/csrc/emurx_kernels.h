@@ -42,13 +42,18 @@ inline hipError_t emurx_launch(void (*k)(P...), dim3 grid, dim3 block, size_t ld
 // bytes); waves whose frames span more than the slab take the window path
 namespace emurx {
 constexpr uint32_t kStageWide = 7168, kStageNarrow = 6144, kStageTight = 5120;
+// k_rx's feedback words: 64 sampled tiles x 4 waves of stage facts, then as many path words
+constexpr uint32_t kFbWords = 256;
 }
 
 // Enqueue one batch on `st`: a single k_rx launch, no host synchronisation (capturable in a
 // hipGraph).  ev[0..1] (optional) are recorded before and after it.  stage: the staging slab
 // per wave in bytes, 7168 (5 workgroups per CU), 6144 (6) or 5120 (7; emurx_parse.h kStage*;
-// every kind has all three).  fb (optional, 64 * 4 device words): the sampled tiles' stage
-// feedback, tagged with gen (29 bits).  Returns 0 or -1.
+// every kind has all three).  fb (optional, 2 * kFbWords device words): the sampled tiles' stage
+// feedback, tagged with gen (29 bits), then one word per sampled wave {gen << 2, the lookups took
+// the uniform-wave path << 1, the parse took it}.  uniform: staged waves whose frames share one
+// plain IPv4 udp / tcp shape take the uniform-wave path (emurx_parse.h); results never depend on
+// it.  Returns 0 or -1.
 // rt (optional, classify only): the route count pass fused into k_rx: per-(tile, owner) counts
 // into cnt[ntiles * 16] and per-group sums added into grp (as emurx_launch_route's first pass).
 // kind: 0 parse only, 1 parse + classify, 2 parse + lookup keys.
@@ -74,7 +79,7 @@ struct emurx_route_args {
 int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n,
                        const emurx_dev_tables& T, int kind, const emurx_dev_out& out,
                        hipStream_t st, const hipEvent_t* ev, uint32_t stage, uint32_t* fb, uint32_t gen,
-                       const emurx_route_args* rt = nullptr);
+                       bool uniform, const emurx_route_args* rt = nullptr);
 
 // One edited 64-byte table block (emurx_api.cpp ship_tables): k_apply copies w to dst.
 struct emurx_delta {

@@ -68,6 +68,7 @@ struct RxArgs {
     uint32_t* flow;
     uint32_t* fb;
     uint32_t gen;
+    uint32_t uniform;  // staged waves of one plain shape take the uniform-wave path
     emurx_route_args rt;
 };
 
@@ -237,7 +238,8 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     // IsUnicastToMe's destination MAC) read the parked words and the frame again; on the window
     // path through a window source built again from the descriptor behind an opaque copy, so the
     // first one ends with the lookup key instead of holding its five registers across the probes
-    auto classify_parked = [&](const auto& s) {
+    auto classify_parked = [&](const auto& s, bool try_uni) {
+        bool done = false;
         if constexpr (kParkRec) {
             typedef std::decay_t<decltype(s)> S;
             volatile uint32_t* pa = &L.csum[wv][lane];
@@ -246,7 +248,12 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
             static_assert(EMURX_FLAG_RTALERT < 8 && EMURX_ST_PANIC_MBUF < 32, "flags and status share the parked byte");
             *pb = r.l7len | (r.nh << 16) | (r.flags << 24) | (r.status << 27);
             r.flags = 0;
-            if (r.status == EMURX_ST_OK) {
+            // a wave of one shape (try_uni: wave-uniform, every lane here): the lookups by the
+            // uniform-wave path where its conditions hold (emurx_parse.h classify_uniform)
+            if constexpr (std::is_same<S, LdsSrc>::value) {
+                if (try_uni) done = classify_uniform(s, T, r);
+            }
+            if (!done && r.status == EMURX_ST_OK) {
                 const LKey k = make_key(s, len, r);
                 const uint32_t l3 = r.l3;
                 auto again = [&]() {
@@ -281,14 +288,31 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
             r.flags |= (wb >> 24) & 7u;
             r.status = wb >> 27;
         }
+        return done;
     };
+    uint32_t uni = 0;
     if (sg.staged) {  // wave-uniform branch
+        // a lane without a frame reads its wave's slab from the start (uniform_shape)
+        LdsSrc s{reinterpret_cast<const uint8_t*>(slab), slab, wv * kStage + (valid ? off - sg.start : 0u)};
+        // the uniform-wave path (emurx_parse.h): one ballot on the frames' shape, then a parse
+        // without divergent control flow; in the classify build a second one on the parse's
+        // outcome and the home slots, then the lookups' result by selects.  uni: bit 0 the parse,
+        // bit 1 the lookups took it (scalars)
+        bool try_uni = false;
+        if (a.uniform) {
+            const UniShape u = uniform_shape(s, valid, len);
+            if (u.ok) {
+                parse_uniform(s, vport, T.cb_mask, u, r);
+                uni = 1;
+                if constexpr (kParkRec) try_uni = true;  // inside classify_parked, with the fields parked
+                else if constexpr (kClassify) uni |= classify_uniform(s, T, r) ? 2u : 0u;
+            }
+        }
         if (valid) {
-            LdsSrc s{reinterpret_cast<const uint8_t*>(slab), slab, wv * kStage + (off - sg.start)};
-            parse_flat(s, len, vport, T.cb_mask, r);
+            if (!(uni & 1)) parse_flat(s, len, vport, T.cb_mask, r);
             STAMP(3);
-            if constexpr (kParkRec) classify_parked(s);
-            else if (kClassify) classify(s, len, T, r);
+            if constexpr (kParkRec) uni |= classify_parked(s, try_uni) ? 2u : 0u;
+            else if (kClassify && !(uni & 2)) classify(s, len, T, r);
             if (kKind == 2) tun = pack_lookup(s, len, r, i, r.status == EMURX_ST_OK, rt.tup_on, lhead, ltail);
         }
     } else {
@@ -299,13 +323,15 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
         coop_checksum_rows(r, a.frames + off, L.csum[wv]);  // the wave's long L4 spans, converged
         STAMP(3);
         if constexpr (kParkRec) {
-            if (valid) classify_parked(s);
+            if (valid) classify_parked(s, false);
         } else if (valid && kClassify) {
             classify(s, len, T, r);
         }
         if (kKind == 2 && valid) tun = pack_lookup(s, len, r, i, r.status == EMURX_ST_OK, rt.tup_on, lhead, ltail);
     }
     STAMP(4);
+    // which path the sampled waves took (emurx_last_uniform): a second word per wave
+    if (a.fb && (tile & 63) == 0 && lane == 0) a.fb[kFbWords + ((tile >> 6) & 63) * kWaves + wv] = (a.gen << 2) | uni;
     // kind 2: the frame's owner, its rank among the wave's frames of that owner, and its tail's
     // units: per (wave, owner) one atomic on the owner's cursor of this tile's shard (a line
     // each) takes the units of the wave's tails (tails of 1 and 3 units ranked by two ballots).
@@ -586,7 +612,7 @@ int emurx_launch_apply(const emurx_delta* d, uint32_t n, hipStream_t st) {
 int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n,
                        const emurx_dev_tables& T, int kind, const emurx_dev_out& out,
                        hipStream_t st, const hipEvent_t* ev, uint32_t stage, uint32_t* fb, uint32_t gen,
-                       const emurx_route_args* rt) {
+                       bool uniform, const emurx_route_args* rt) {
     using namespace emurx;
     hipError_t e = hipSuccess;
 #ifndef EMURX_RX_LDS_PAD  // measurement builds only: unused LDS per workgroup, to cap k_rx's occupancy
@@ -598,7 +624,7 @@ int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n
         unsigned long long* hist = reinterpret_cast<unsigned long long*>(out.hist);
         const emurx_route_args none{};
         const RxArgs args{frames, desc, n, T, out.rec, out.qlist, out.qcap, out.tile_cnt, hist, out.flow, fb, gen,
-                          rt ? *rt : none};
+                          uniform ? 1u : 0u, rt ? *rt : none};
         // every kind has the tight slab: at 7 waves per SIMD (72 VGPRs) kinds 0 and 2 compile
         // without scratch as they are (58 and 69 VGPRs), kind 1 with its record fields parked
         // (tile_body kParkRec, 71), so a tight choice never maps to another size

@@ -1545,6 +1545,143 @@ __device__ __forceinline__ void classify(const S& s, uint32_t len, const emurx_d
     resolve(T, r, k, [&](uint32_t cid) { return flow_probe(T, get_tuple(s, len, r), cid); });
 }
 
+// ---------------------------------------------------------------------------------------
+// The uniform-wave path (staged waves, k_rx tile_body).  One port's traffic mostly fills a wave
+// with frames of one shape: the same number of 802.1Q tags, IPv4 without options or fragments,
+// one of UDP / TCP, each frame exactly as long as its total length says.  uniform_shape decides
+// that for the whole wave with one ballot; parse_uniform then restates parse_flat for such a
+// wave with the L3 offset, the tag count and the protocol as scalars and no divergent control
+// flow (selects and scalar branches only), and classify_uniform restates classify for a wave
+// whose lanes all reached the plain udp / tcp callback and hit the first slot of their home
+// buckets.  The rule that keeps this checkable: a fact the straight-line code assumes and a
+// lane does not meet sends the whole wave to the generic code of that stage; no lane is ever
+// patched.  What is still decided per lane, by selects: the IPv4 header checksum, the UDP
+// checksum-present rule, the L4 checksum, TCP's data offset against its segment, the port rule
+// that picks the callback, the callback mask.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t wave_first(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+struct UniShape {
+    uint32_t tags, l3, nh;  // scalars: 802.1Q / QinQ tags (0..2), L3 offset, IPv4 protocol (6 or 17)
+    uint32_t totlen;        // the lane's IPv4 total length
+    bool ok;                // scalar: every lane of the wave has this shape
+};
+// Called by the whole wave.  `s` of a lane without a frame may point anywhere in the slab.
+// A passing lane has len == l3 + totlen and totlen >= 20 + the L4 header, so none of the
+// length checks of parse_flat / parse_l4_flat can fire (nor span_ok: no 16-bit wrap)
+__device__ __forceinline__ UniShape uniform_shape(const LdsSrc& s, bool valid, uint32_t len) {
+    auto is_tag = [](uint32_t x) { return x == 0x8100 || x == 0x88A8; };
+    UniShape u{0, 0, 0, 0, false};
+    // mixed traffic leaves at the first ballot, two byte reads in: one first EtherType / TPID
+    // for the wave (stricter than one tag count; a port's tags carry one TPID)
+    const uint32_t e0 = be16(s, 12), e0w = wave_first(e0);
+    if (__ballot(!valid || e0 != e0w)) return u;
+    uint32_t nt = 0;
+    if (is_tag(e0w)) nt = is_tag(be16(s, 16)) ? 2u : 1u;  // an untagged wave reads no second TPID
+    u.tags = wave_first(nt);
+    u.l3 = 14 + 4 * u.tags;
+    // with the lane's own tag count (checked below) bytes l3 - 2, l3 - 1 are its last EtherType:
+    // a third tag or PPPoE is not 0x0800
+    const uint32_t et = be16(s, u.l3 - 2), b0 = s.u8(u.l3), frag = be16(s, u.l3 + 6), nh = s.u8(u.l3 + 9);
+    u.totlen = be16(s, u.l3 + 2);
+    u.nh = wave_first(nh);
+    const uint32_t need = u.nh == 6 ? 40u : 28u;
+    const bool pass = valid && nt == u.tags && et == 0x0800 && b0 == 0x45 && (frag & 0x3fff) == 0 && nh == u.nh &&
+                      len == u.l3 + u.totlen && u.totlen >= need;
+    u.ok = (u.nh == 6 || u.nh == 17) && __ballot(pass) == ~0ull;
+    return u;
+}
+// dword_sum over bytes [at, at + n) of every lane's frame, n >= 8.  When the wave shares n and
+// the span's alignment in its dword (dense frames of one size), the masks and the trip count are
+// scalars: one sad per dword and a scalar loop.  The same dwords under the same masks, so the
+// same integer as dword_sum
+__device__ __forceinline__ uint32_t span_sum_wave(const LdsSrc& s, uint32_t at, uint32_t n) {
+    const uint32_t a = s.base + at;
+    const uint32_t sa = wave_first(a & 3), sn = wave_first(n);
+    if (__ballot((a & 3) != sa || n != sn)) return s.sum(at, n);
+    const uint32_t e = sa + sn, last = (e - 1) >> 2;  // >= 1
+    const uint32_t hm = 0xffffffffu << (8 * sa), tm = 0xffffffffu >> (8 * ((0u - e) & 3));
+    const uint32_t* w = s.b32 + (a >> 2);
+    uint32_t acc = sad16(w[0] & hm, 0), j = 1;
+    for (; j + 4 <= last; j += 4) {
+        const uint32_t x0 = w[j], x1 = w[j + 1], x2 = w[j + 2], x3 = w[j + 3];
+        acc = sad16(x3, sad16(x2, sad16(x1, sad16(x0, acc))));
+    }
+    for (; j < last; ++j) acc = sad16(w[j], acc);
+    return sad16(w[last] & tm, acc);
+}
+// parse_flat for a wave of shape u: field values on every outcome equal parse_flat's
+__device__ __forceinline__ void parse_uniform(const LdsSrc& s, uint32_t vport, uint32_t cb_mask, const UniShape& u, Rec& r) {
+    const uint32_t L3 = u.l3, L4 = L3 + 20, l4len = u.totlen - 20;
+    r.ns = EMURX_ID_NONE; r.cl = EMURX_ID_NONE;
+    r.vlan0 = u.tags >= 1 ? (be32(s, 12) & 0xffff0fffu) : 0u;
+    r.vlan1 = u.tags == 2 ? (be32(s, 16) & 0xffff0fffu) : 0u;
+    r.vport = vport;
+    r.l3 = L3;
+    r.flags = 0;
+    r.dlen = 0;
+    r.flow = EMURX_FLOW_NONE;
+    const bool hok = csum_ok(s.template sum_fixed<20>(L3), s.at(L3), 0);
+    const uint32_t pcs = be_domain(s.template sum_fixed<8>(L3 + 12), s.at(L3 + 12)) + u.nh + l4len;  // src, dst, 0|proto, len
+    // summed for every lane (a lane Go would not sum ignores the verdict)
+    const bool cs = csum_ok(span_sum_wave(s, L4, l4len), s.at(L4), pcs);
+    uint32_t st, cb, l7, l7len;
+    if (u.nh == 17) {  // scalar
+        const bool ucs = (s.u8(L4 + 6) | s.u8(L4 + 7)) != 0;  // UDP checksum present
+        st = ucs && !cs ? EMURX_ST_UDP_CS : EMURX_ST_OK;
+        l7len = (l4len - 8) & 0xffff;
+        l7 = st == EMURX_ST_OK ? L4 + 8 : 0u;
+        const uint32_t src = be16(s, L4), dst = be16(s, L4 + 2);
+        cb = dst == 5353 ? EMURX_CB_MDNS
+           : (src == 67 && dst == 68) ? EMURX_CB_DHCP
+           : (dst == 67 && (src == 67 || src == 68)) ? EMURX_CB_DHCPSRV : EMURX_CB_UDP;
+    } else {  // TCP: L7 / L7Len are set once the data offset fits the segment, before the checksum
+        const uint32_t tcplen = (s.u8(L4 + 12) >> 4) << 2;
+        const bool fits = l4len >= tcplen;
+        st = !fits ? EMURX_ST_TCP_TOO_SHORT : !cs ? EMURX_ST_TCP_CS : EMURX_ST_OK;
+        l7len = fits ? ((l4len - tcplen) & 0xffff) : 0u;
+        l7 = fits ? ((L4 + tcplen) & 0xffff) : 0u;
+        cb = EMURX_CB_TCP;
+    }
+    // a failed header checksum returns before anything of L4 is set
+    st = hok ? st : (uint32_t)EMURX_ST_IPV4_CS;
+    r.l4 = hok ? L4 : 0u;
+    r.nh = hok ? u.nh : 0u;
+    r.l7 = hok ? l7 : 0u;
+    r.l7len = hok ? l7len : 0u;
+    // invoke() / fail(); neither callback is EAPOL
+    r.proto = st == EMURX_ST_OK ? cb : (uint32_t)EMURX_CB_NONE;
+    r.status = st != EMURX_ST_OK ? st : ((cb_mask >> cb) & 1u) ? (uint32_t)EMURX_ST_OK : (uint32_t)EMURX_ST_NOT_SUPPORTED;
+}
+// classify for a wave whose lanes all reached the plain udp / tcp callback: CLookupByMac of the
+// destination MAC (make_key's default rule).  Only the first slot of the two home buckets is
+// read (16 bytes each instead of 64): where every lane's Namespace and client sit there, with the
+// Namespace's transport plugin and no transport flow to resolve, the outcome is resolve_done's
+// for kMac.  Any other lane (a zero, broadcast or unknown MAC, an unknown Namespace, a key past
+// the first slot, a client with a TransportCtx while flows are resolved): false, nothing
+// written, and the caller runs classify for the wave
+__device__ __forceinline__ bool classify_uniform(const LdsSrc& s, const emurx_dev_tables& T, Rec& r) {
+    const bool plain = r.status == EMURX_ST_OK && (r.proto == EMURX_CB_UDP || r.proto == EMURX_CB_TCP);
+    if (__ballot(!plain)) return false;
+    const uint32_t lo = le32(s, 0), hi = s.u8(4) | (s.u8(5) << 8);
+    const uint32_t tk = emurx_tk_hash(r.vport, r.vlan0, r.vlan1);
+    const uint4 x = gld16(T.ns_tab + (size_t)(tk & T.ns_mask) * EMURX_BUCKET_WORDS);
+    const uint4 y = gld16(T.mac_tab + (size_t)(emurx_mac_hash(tk, lo, hi) & T.mac_mask) * EMURX_BUCKET_WORDS);
+    const uint32_t plug = 1u << EMURX_PLUG_TRANSPORT;
+    static_assert(kCbPluginTab[EMURX_CB_UDP] == EMURX_PLUG_TRANSPORT && kCbPluginTab[EMURX_CB_TCP] == EMURX_PLUG_TRANSPORT,
+                  "udp and tcp check the transport plugin");
+    const bool ns_hit = x.w != EMURX_EMPTY && (x.x & 0xffffu) == r.vport && x.y == r.vlan0 && x.z == r.vlan1 &&
+                        ((x.x >> 16) & plug);
+    const bool cl_hit = y.w != EMURX_EMPTY && y.x == x.w && y.y == lo && (y.z & 0xffffu) == hi;
+    const bool flows = T.ft_on && ((y.z >> 16) & EMURX_CPL_CTX);
+    if (__ballot(!((lo | hi) != 0 && ns_hit && cl_hit && !flows))) return false;
+    r.ns = x.w;
+    r.cl = y.w;
+    const bool has = (y.z >> 16) & plug;
+    set_lk(r, has ? EMURX_LK_CLIENT : EMURX_LK_CLIENT_NO_PLUGIN);
+    r.flow = has ? EMURX_FLOW_NO_CTX : r.flow;
+    return true;
+}
+
 // ---- partitioned path: the lookup record (include/emu_rx.h emurx_lookup_rec) -----------
 // Everything the owner needs to finish the frame: a 32-byte head, and for two classes a tail
 // of 16-byte units in the region's tail shards (emu_rx.h).  Head words:

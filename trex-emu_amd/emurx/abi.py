@@ -212,6 +212,7 @@ SIGNATURES = [
     ("emurx_set_timing", C.c_int, [_P, C.c_uint32, C.c_uint32]),
     ("emurx_kernel_times", C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("emurx_last_stage", C.c_uint32, [_P]),
+    ("emurx_last_uniform", C.c_int, [_P, _P]),
     ("emurx_last_txz", C.c_int32, [_P]),
     ("emurx_copy_ceiling_dev", C.c_int, [_P, _P, C.c_size_t, _P]),
     ("emurx_ns_owner", C.c_uint32, [_U8P, C.c_uint32]),
@@ -258,6 +259,11 @@ SIGNATURES = [
                                      C.POINTER(C.c_uint64), _P]),
 ]
 
+# measurement observables that an older library given through EMURX_LIB (A/B runs of one
+# bench.py against two builds) may lack; calling one it lacks is an AttributeError
+OPTIONAL = {"emurx_last_uniform"}
+UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
+
 _lib = None
 
 
@@ -272,7 +278,10 @@ def load(path: str | os.PathLike | None = None):
                       "(there is no CPU fallback for the product path)")
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None and name in OPTIONAL and "EMURX_LIB" in os.environ and path is None:
+            continue
+        fn = fn or getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     if path is None:

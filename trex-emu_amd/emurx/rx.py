@@ -201,6 +201,14 @@ class RxPath:
         """LDS staging bytes per wave of the most recent k_rx launch (7168 or 6144)."""
         return int(self.lib.emurx_last_stage(self.h))
 
+    def last_uniform(self) -> np.ndarray:
+        """Which path the sampled waves of the most recent k_rx launch took (waits for the
+        device): 256 words, [(tile // 64 % 64) * 4 + wave] = abi.UNI_SAMPLED | abi.UNI_PARSE |
+        abi.UNI_LOOKUP for a sampled wave (the waves of every 64th tile), 0 otherwise."""
+        w = np.zeros(abi.UNI_WORDS, np.uint32)
+        abi.check(self.lib.emurx_last_uniform(self.h, _p(w)), "last_uniform")
+        return w
+
     def last_txz(self) -> int:
         """LDS image bytes per wave of the last tx framing write (6144, 4608, 0; -1 before)."""
         return int(self.lib.emurx_last_txz(self.h))
