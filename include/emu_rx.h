@@ -382,6 +382,14 @@ int emurx_image_lookup(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t
    from the last bucket to bucket 0, out[5] tombstone slots it passed.  A mac / ipv4 / ipv6 key
    whose Namespace is not alive reads no bucket: EMURX_ENOENT, out all zero. */
 int emurx_image_probe(emurx_t* h, uint32_t table, const uint32_t* key, uint32_t out[6]);
+/* The hash emurx_learn_dev's two sets place a key by (tests that need keys at chosen places of
+   the sets: chains, the step from the last slot to slot 0, owners with an equal tag).  key: the
+   key's seven words as the kernels hold them: ns id, the IP as four little-endian words (ARP: the
+   IPv4 address, then zeros), the MAC's bytes 0..3, its bytes 4..5 | kind (EMURX_LRN_*) << 16.
+   The workgroup's set of 512 slots starts the key at (h >> 9) & 511; the global set of a batch
+   of n frames has the smallest power of two >= max(128, 2 n) slots, starts the key at
+   h & (slots - 1) and tags the slot's owner with h >> 27; both probe linearly and wrap. */
+uint32_t emurx_learn_key_hash(const uint32_t key[7]);
 /* Compare the device tables with the host image after a shipment (synchronises the handle's
    stream): *mismatched = 32-bit words that differ. */
 int emurx_image_check(emurx_t* h, uint64_t* mismatched);

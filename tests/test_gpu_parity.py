@@ -811,6 +811,64 @@ def test_ingest_small_limits(rxmod, small, monkeypatch):
         assert run(msgs, offs) == (small == "1" and fits), (flen, fits)
 
 
+def _msg_slots(m):
+    """The descriptor slots the framing walk gives a message: what it announces, as far as a
+    message of its length can carry (64 KiB of it at most)."""
+    if len(m) < 4 or m[:2] != b"\xbe\xef":
+        return 0
+    return min(int.from_bytes(m[2:4], "big"), (min(len(m), 65536) - 4) // 4)
+
+
+@pytest.mark.parametrize("full,per", [(2049, 2), (4120, 3)])
+def test_ingest_scan_several_tiles_per_lane(rxmod, full, per, monkeypatch):
+    """The pipeline's queue scan (k_qscan: 512 lanes, each with ceil(tiles / 512) consecutive
+    tiles) with more than one tile per lane: 2,049 messages of 64 config C frames are 513 tiles,
+    two per lane and most lanes past the last tile; 4,120 are 1,030 tiles, three per lane with a
+    ragged last lane.  Hostile and empty messages among them, at unaligned offsets.  A lane's
+    second tile starts where its first ends in every queue: the frames spread over at least four
+    queues, and some queue has entries in two tiles of one lane."""
+    import test_abi
+    monkeypatch.setenv("EMURX_INGEST_SMALL", "0")
+    rng = np.random.default_rng(0x95CA + full)
+    w = synth.config_c(8192, seed=0xC0DE)
+    frames = [w["buf"][d["off"]:d["off"] + d["len"]].tobytes() for d in w["desc"]]
+    vports = [int(v) for v in w["desc"]["vport"]]
+    rx, o = new_pair(rxmod, max_frames=1 << 19)
+    for t in (rx, o):
+        synth.load_tables(w, t)
+    nf = len(frames)
+    pick = lambda i: [(64 * i + j) % nf for j in range(64)]  # noqa: E731
+    msgs = [F.zmq_pack([frames[k] for k in pick(i)], [vports[k] for k in pick(i)]) for i in range(full)]
+    hostile = test_abi._rand_msgs(rng, 12) + [b"", b"", b""]
+    for m, at in zip(hostile, sorted(int(x) for x in rng.integers(0, full, len(hostile)))):
+        msgs.insert(at, m)
+    base = np.concatenate([[0], np.cumsum([_msg_slots(m) for m in msgs])])
+    nt = -(-int(base[-1]) // abi.QUEUE_TILE)
+    assert int(base[-1]) >= 64 * full and -(-nt // 512) == per
+    if per == 2:
+        assert nt in (513, 514) and -(-nt // per) < 260  # lanes 257 .. 511 are past the last tile
+    else:
+        assert nt in (1030, 1031) and nt % per != 0      # the last lane with tiles has fewer than three
+    tab = place_messages(rx, 0, msgs, rng)
+    rx.ingest_submit(0, tab)
+    res = rx.ingest_wait(0)
+    assert not res["one_launch"]
+    check_ingest(res, o, msgs, tab)
+    # which queues the tiles of one lane hold: slot = the message's first slot + the frame's index
+    nfr = res["msg_frames"].astype(np.int64)
+    assert res["n"] == nfr.sum() >= 64 * full
+    slot = np.repeat(base[:-1] - np.concatenate([[0], np.cumsum(nfr)[:-1]]), nfr) + np.arange(res["n"])
+    rec = res["rec"]
+    q = np.where(rec["status"] == 0, rec["proto"], abi.Q_DROP).astype(np.int64)
+    tile = slot // abi.QUEUE_TILE
+    cnt = np.zeros((nt, abi.NUM_QUEUES), np.int64)
+    np.add.at(cnt, (tile, q), 1)
+    assert ((cnt > 0).any(0)).sum() >= 4
+    both = (cnt[:-1] > 0) & (cnt[1:] > 0) & ((np.arange(nt - 1) // per == np.arange(1, nt) // per)[:, None])
+    assert both.any(0).sum() >= 4  # in four queues a lane's later tile starts behind entries of its earlier one
+    rx.close()
+
+
 def test_ingest_messages(rxmod):
     """Valid, truncated, corrupted, over-announcing, oversized and > 64 KiB messages in one
     batch at unaligned offsets: records, descriptors, queues, per-message frame counts and

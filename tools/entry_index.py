@@ -52,7 +52,7 @@ GROUPS = [
     ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev"],
      "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`, "
      "`NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
-    ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events"],
+    ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events", "emurx_learn_key_hash"],
      "`PluginArpNs.ArpLearn` `arp/arp.go:886-901`, `NdLearn` `ipv6/nd.go:1611-1620`, `:1687-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_uniform", "emurx_last_txz"],

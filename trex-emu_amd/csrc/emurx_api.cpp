@@ -1458,6 +1458,10 @@ int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_des
 
 uint32_t emurx_learn_max_events(const emurx_t* h) { return h ? emurx_lrn_slots(h->cfg.max_frames) / 2 : 0; }
 
+uint32_t emurx_learn_key_hash(const uint32_t key[7]) {
+    return key ? emurx_lrn_hash(key[0], key[1], key[2], key[3], key[4], key[5], key[6]) : 0;
+}
+
 int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
                     uint32_t kinds, emurx_learn_ev* d_ev, uint32_t ev_cap, uint8_t* d_outcome, uint64_t* d_info,
                     void* stream) {

@@ -57,14 +57,8 @@ struct LrnPlan {
 };
 __device__ __forceinline__ LrnPlan lrn_plan(uint32_t outcome) { return {outcome, {0, {0, 0, 0, 0}, 0, 0}}; }
 __device__ __forceinline__ bool lrn_learns(uint32_t outcome) { return outcome >= EMURX_LRN_ARP_REQ && outcome <= EMURX_LRN_ND_NA; }
-__device__ __forceinline__ uint32_t lrn_hash(const LrnKey& k) {
-    uint32_t h = k.ns * 0x9E3779B1u ^ k.mhk;
-    h = (h ^ k.ip[0]) * 0x85EBCA6Bu;
-    h = (h ^ (h >> 15) ^ k.ip[1]) * 0xC2B2AE35u;
-    h = (h ^ (h >> 13) ^ k.ip[2]) * 0x27D4EB2Fu;
-    h = (h ^ (h >> 16) ^ k.ip[3]) * 0x165667B1u;
-    h = (h ^ (h >> 15) ^ k.mlo) * 0x85EBCA6Bu;
-    return h ^ (h >> 16);
+__device__ __forceinline__ uint32_t lrn_hash(const LrnKey& k) {  // emurx_tables.h: the host calls it too
+    return emurx_lrn_hash(k.ns, k.ip[0], k.ip[1], k.ip[2], k.ip[3], k.mlo, k.mhk);
 }
 
 // The record's words: as in emurx_respond.hip

@@ -97,6 +97,20 @@ EMURX_HD uint32_t emurx_srv_hash(uint32_t cid, uint32_t port_proto) {
     return emurx_hash(cid, port_proto, 0x737276u, 0, 0);
 }
 
+// The learning fold's key hash (emurx_learn.hip) over the key's seven words: ns, ip[0..3], the
+// MAC's bytes 0..3 (mlo), its bytes 4..5 | kind << 16 (mhk).  The workgroup's set starts a key's
+// probe at (h >> 9) & 511, the global set at h & mask, and tags the owner word with h >> 27.
+EMURX_HD uint32_t emurx_lrn_hash(uint32_t ns, uint32_t ip0, uint32_t ip1, uint32_t ip2, uint32_t ip3, uint32_t mlo,
+                                 uint32_t mhk) {
+    uint32_t h = ns * 0x9E3779B1u ^ mhk;
+    h = (h ^ ip0) * 0x85EBCA6Bu;
+    h = (h ^ (h >> 15) ^ ip1) * 0xC2B2AE35u;
+    h = (h ^ (h >> 13) ^ ip2) * 0x27D4EB2Fu;
+    h = (h ^ (h >> 16) ^ ip3) * 0x165667B1u;
+    h = (h ^ (h >> 15) ^ mlo) * 0x85EBCA6Bu;
+    return h ^ (h >> 16);
+}
+
 struct emurx_dev_tables {
     const uint32_t* ns_tab;   // [ns_mask + 1] buckets of 4 slots
     const uint32_t* ns_info;  // 4 words per ns id
