@@ -588,25 +588,26 @@ bool small_fits(const uint32_t* ctl, uint32_t nmsg, uint32_t n, uint32_t max_til
 // the result block of a batch of n descriptor slots and nmsg messages (256-byte aligned parts):
 // allocates both copies and points the views into them
 int set_results(IngestSlot& s, uint32_t n, uint32_t nmsg) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_desc = al((size_t)n * sizeof(emurx_rec)), o_q = o_desc + al((size_t)n * sizeof(emurx_desc));
-    const size_t o_stat = o_q + al((size_t)n * 4), o_qoff = o_stat + al((size_t)nmsg * 4), o_hist = o_qoff + 256;
-    const size_t total = o_hist + 2 * EMURX_HIST_BINS * sizeof(uint64_t);
+    // one layout for both copies (and, over no block, for their size)
+    auto carve = [&](uint8_t* block, View<emurx_rec>& rec, View<emurx_desc>& desc, View<uint32_t>& q,
+                     View<uint32_t>& stat, View<uint32_t>& qoff, View<uint64_t>& hist) {
+        emurx_carver c(block);
+        rec.p = c.take<emurx_rec>(n);
+        desc.p = c.take<emurx_desc>(n);
+        q.p = c.take<uint32_t>(n);
+        stat.p = c.take<uint32_t>(nmsg);
+        qoff.p = c.take<uint32_t>(EMURX_NUM_QUEUES + 1);
+        hist.p = c.take<uint64_t>(2 * EMURX_HIST_BINS);
+        return c.bytes();
+    };
+    View<emurx_rec> rec;
+    View<emurx_desc> desc;
+    View<uint32_t> q, stat, qoff;
+    View<uint64_t> hist;
+    const size_t total = carve(nullptr, rec, desc, q, stat, qoff, hist);
     if (s.h_res.alloc(total) || s.d_res.alloc(total)) return EMURX_ENOMEM;
-    uint8_t* hb = s.h_res.p;
-    uint8_t* db = s.d_res.p;
-    s.h_rec.p = reinterpret_cast<emurx_rec*>(hb);
-    s.h_desc.p = reinterpret_cast<emurx_desc*>(hb + o_desc);
-    s.h_qlist.p = reinterpret_cast<uint32_t*>(hb + o_q);
-    s.h_stat.p = reinterpret_cast<uint32_t*>(hb + o_stat);
-    s.h_qoff.p = reinterpret_cast<uint32_t*>(hb + o_qoff);
-    s.h_hist.p = reinterpret_cast<uint64_t*>(hb + o_hist);
-    s.d_rec.p = reinterpret_cast<emurx_rec*>(db);
-    s.d_desc.p = reinterpret_cast<emurx_desc*>(db + o_desc);
-    s.d_packed.p = reinterpret_cast<uint32_t*>(db + o_q);
-    s.d_stat.p = reinterpret_cast<uint32_t*>(db + o_stat);
-    s.d_qoff.p = reinterpret_cast<uint32_t*>(db + o_qoff);
-    s.d_hist_out.p = reinterpret_cast<uint64_t*>(db + o_hist);
+    carve(s.h_res.p, s.h_rec, s.h_desc, s.h_qlist, s.h_stat, s.h_qoff, s.h_hist);
+    carve(s.d_res.p, s.d_rec, s.d_desc, s.d_packed, s.d_stat, s.d_qoff, s.d_hist_out);
     s.res_bytes = total;
     return EMURX_OK;
 }

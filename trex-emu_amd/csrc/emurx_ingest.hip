@@ -111,17 +111,6 @@ __global__ __launch_bounds__(kBlock) void k_zmq_walk(const uint8_t* __restrict__
     msg_stat[m] = found | (err << 24);
 }
 
-// inclusive wave64 prefix sum
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t o = 1; o < kWave; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)v, o);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
 __device__ __forceinline__ void tile_row(const uint32_t* tile_cnt, uint32_t t, uint32_t r[EMURX_NUM_QUEUES]) {
     const uint4* row = reinterpret_cast<const uint4*>(tile_cnt + (size_t)t * 16);
     const uint4 a = row[0], b = row[1], c = row[2], d = row[3];
@@ -153,7 +142,8 @@ __global__ __launch_bounds__(kScanLanes) void k_qscan(const uint32_t* __restrict
     uint32_t ex[EMURX_NUM_QUEUES];
 #pragma unroll
     for (int q = 0; q < EMURX_NUM_QUEUES; ++q) {
-        const uint32_t incl = wave_incl_scan(v[q]);
+        uint32_t incl = v[q];
+        wave_incl_scan(incl);
         ex[q] = incl - v[q];
         if (lane == kWave - 1) s_w[wv][q] = incl;
     }
@@ -326,13 +316,9 @@ __global__ __launch_bounds__(kBlock) void k_ingest_small(const SmallArgs a) {
                 v = mk.y ? (((mk.x & 15u) + mk.y + 15u) >> 4) + 2u : 0u;  // + 32 B of slack
             }
             uint32_t incl = v;
-#pragma unroll
-            for (uint32_t o = 1; o < kWave; o <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-                if (lane >= o) incl += up;
-            }
+            wave_incl_scan(incl);
             if (k < nm) s_vec[k] = vb + incl - v;
-            vb += (uint32_t)__shfl((int)incl, kWave - 1);
+            vb += wave_last(incl);
             nv = vb;
         }
         if (lane == 0) s_vec[nm] = nv;
@@ -359,7 +345,7 @@ __global__ __launch_bounds__(kBlock) void k_ingest_small(const SmallArgs a) {
                                          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint4*>(s_msg) + c),
                                          16, 0, 0);
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's rows landed
+    wait_vm0();  // vmcnt(0): this wave's rows landed
     __syncthreads();
     SSTAMP(3);
     // 2. the walk of OnRxStream (veth_zmq.go:277-320), in LDS.  A frame's step notes only its
@@ -575,7 +561,8 @@ __global__ __launch_bounds__(kBlock) void k_ingest_small(const SmallArgs a) {
         }
 #pragma unroll
         for (uint32_t j = 0; j < kPer; ++j) sum += c4[j];
-        const uint32_t incl = wave_incl_scan(sum);
+        uint32_t incl = sum;
+        wave_incl_scan(incl);
         if (lane == kWave - 1) s_wsum[wv] = incl;
         __syncthreads();
         uint32_t at = incl - sum, total = 0;

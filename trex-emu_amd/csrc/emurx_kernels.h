@@ -1,4 +1,5 @@
-// emurx_kernels.h — launcher of the rx parse / classify / queue kernel (emurx_kernels.hip).
+// emurx_kernels.h — the host side's view of the device passes: the HIP status check, the
+// launch wrapper, the scratch carver and the launchers of every .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,25 @@ inline hipError_t emurx_launch(void (*k)(P...), dim3 grid, dim3 block, size_t ld
         },
         args);
 }
+
+// Carves one block of memory into typed regions that each start on a 256-byte boundary:
+// take<T>(n) is the next region, n elements of T; bytes() the size of all regions taken so
+// far.  With a null base it hands out null pointers and only counts, so one layout function
+// gives both the size a block needs and the pointers into it.
+class emurx_carver {
+    uint8_t* base_;
+    size_t at_ = 0;
+
+public:
+    explicit emurx_carver(void* base) : base_(static_cast<uint8_t*>(base)) {}
+    template <typename T>
+    T* take(size_t n) {
+        T* p = base_ ? reinterpret_cast<T*>(base_ + at_) : nullptr;
+        at_ += (n * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+    size_t bytes() const { return at_; }
+};
 
 // LDS bytes staged per wave (64 frames; emurx_kernels.hip), three sizes chosen per launch.
 // 7 KiB keeps a workgroup's LDS under 32 KiB, so five workgroups (20 waves) fit a CU;

@@ -30,7 +30,6 @@ __device__ __forceinline__ void glds16(const uint4* src, uint4* dst_wave_base) {
     __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0,
                                      kNt ? 2 : 0);
 }
-__device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0)
 
 // Timeline stamps (measurement-only build, -DEMURX_STAMP=1; tools/stamps.py): per wave the
 // shader clock at entry, after the descriptors, after the staging, after the parse, after the
@@ -125,9 +124,7 @@ __device__ __forceinline__ Stage stage_issue(const uint8_t* __restrict__ frames,
 // barrier (each wave reads only its own slab)
 __device__ __forceinline__ void stage_wait() {
     wait_vm0();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 }
 
 // EMURX_MATCHRANK (build variant, A/B): rank the lanes of a queue / an owner by one ballot
@@ -205,7 +202,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     // wait (k_rx): in flight beside the tile's LDS-DMA instead of one more round trip here
     if (kKind == 2 && wv == 0) {
         const TileOffLoads t = EMURX_TOL_PREFETCH ? tol : tile_offsets_issue(rt.cnt, rt.goff, rt.parts, tile, lane);
-        tile_offsets_sum(t, rt.parts, lane, L.toff, [](uint32_t v) { return wave_sum_u32(v); });
+        tile_offsets_sum(t, rt.parts, lane, L.toff);
     }
     const bool valid = (dd.y >> 24) != EMURX_DESC_HOLE;
     const uint32_t off = dd.x, len = dd.y & 0xffff, vport = (dd.y >> 16) & 0xff;
@@ -458,9 +455,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
         park[2 * lane + 1] = valid ? make_uint4(r.vport | (r.l3 << 16), r.l4 | (r.l7 << 16),
                                                 r.l7len | (r.nh << 16) | (r.proto << 24), r.status | (r.flags << 8))
                                    : make_uint4(0, 0, (uint32_t)EMURX_CB_NONE << 24, EMURX_ST_HOLE);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const uint32_t r0 = tile * EMURX_QUEUE_TILE + wv * kWave;  // the wave's first record
         uint4* o = reinterpret_cast<uint4*>(a.rec + r0);
         const uint4 x0 = park[lane], x1 = park[kWave + lane];
@@ -503,9 +498,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     if constexpr (kKind == 2) {  // every frame's 32-byte lookup head into its owner's region
         if (!tails_out) {
             store_tails();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the patched heads, read by other lanes
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();  // the patched heads, read by other lanes
         }
         // the head's slot in send, in 32-byte units (regions of cap + 32 tcap of them: the
         // launcher checks that the whole buffer's units fit 32 bits); none on overflow

@@ -371,11 +371,9 @@ __global__ __launch_bounds__(kBlock) void k_lrn_mark(const uint4* __restrict__ s
 __global__ __launch_bounds__(kLrnScanBlock) void k_lrn_scan(const uint2* __restrict__ tsum, const uint32_t* __restrict__ tcnt,
                                                             uint32_t ntiles, uint32_t ev_cap, uint32_t* __restrict__ tord,
                                                             unsigned long long* __restrict__ info) {
-    __shared__ uint32_t s_w[kLrnScanBlock / kWave];
-    __shared__ uint32_t s_tot;
+    __shared__ BlockScanLds<kLrnScanBlock, uint32_t> s_scan;
     __shared__ uint32_t s_oc[5];
     if (threadIdx.x < 5) s_oc[threadIdx.x] = 0;
-    const uint32_t lane = lane_id(), wv = threadIdx.x / kWave;
     uint32_t base = 0, oc[5] = {0, 0, 0, 0, 0};
     for (uint32_t t0 = 0; t0 < ntiles; t0 += kLrnScanBlock) {  // workgroup-uniform trip count
         const uint32_t t = t0 + threadIdx.x;
@@ -387,24 +385,14 @@ __global__ __launch_bounds__(kLrnScanBlock) void k_lrn_scan(const uint2* __restr
         oc[3] += v.y & 0x3ffu;
         oc[4] += v.y >> 10;
         uint32_t c = cnt;
-#pragma unroll
-        for (uint32_t d = 1; d < kWave; d <<= 1) {
-            const uint32_t u = (uint32_t)__shfl_up((int)c, d);
-            if (lane >= d) c += u;
-        }
-        __syncthreads();  // the previous round's readers
-        if (lane == kWave - 1) s_w[wv] = c;
-        __syncthreads();
-        for (uint32_t w = 0; w < wv; ++w) c += s_w[w];
+        const auto [total] = block_incl_scan<kLrnScanBlock>(s_scan, c);
         if (t < ntiles) tord[t] = base + c - cnt;
-        if (threadIdx.x == kLrnScanBlock - 1) s_tot = c;
-        __syncthreads();
-        base += s_tot;
+        base += total;
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const uint32_t s = wave_sum_u32(oc[k]);
-        if (lane == 0 && s) atomicAdd(&s_oc[k], s);
+        if (lane_id() == 0 && s) atomicAdd(&s_oc[k], s);
     }
     __syncthreads();
     if (threadIdx.x < EMURX_LRN_INFO_WORDS) {
@@ -451,16 +439,25 @@ __global__ __launch_bounds__(kBlock) void k_lrn_emit(const uint8_t* __restrict__
 // scratch: the set uint4 [slots], then slot indices u32 [max_frames], tile sums uint2, tile
 // emitters u32 and tile ordinals u32 [tiles of max_frames].  The set starts, and every call
 // leaves it, all zero.
-static size_t lrn_align(size_t x) { return (x + 255) & ~(size_t)255; }
 uint32_t emurx_lrn_slots(uint32_t max_frames) {
     uint32_t s = 128;
     while (s < 2ull * max_frames && s < (1u << 27)) s <<= 1;
     return s;
 }
-size_t emurx_lrn_scratch_bytes(uint32_t max_frames) {
-    const size_t nt = ((size_t)max_frames + emurx::kLrnTile - 1) / emurx::kLrnTile;
-    return (size_t)emurx_lrn_slots(max_frames) * 16 + lrn_align((size_t)max_frames * 4) + lrn_align(nt * 8) + 2 * lrn_align(nt * 4);
+struct LrnScratch {
+    uint4* slots;
+    uint32_t* slot_of;
+    uint2* tsum;
+    uint32_t *tcnt, *tord;
+    size_t bytes;
+};
+static LrnScratch lrn_scratch(void* base, uint32_t max_frames) {
+    const size_t mt = ((size_t)max_frames + emurx::kLrnTile - 1) / emurx::kLrnTile;
+    emurx_carver c(base);  // the initialisers run in order; the set (a power of two >= 2 KiB) takes no padding
+    return {c.take<uint4>(emurx_lrn_slots(max_frames)), c.take<uint32_t>(max_frames), c.take<uint2>(mt),
+            c.take<uint32_t>(mt), c.take<uint32_t>(mt), c.bytes()};
 }
+size_t emurx_lrn_scratch_bytes(uint32_t max_frames) { return lrn_scratch(nullptr, max_frames).bytes; }
 
 int emurx_launch_learn(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n, uint32_t kinds,
                        const emurx_dev_tables& T, emurx_learn_ev* ev, uint32_t ev_cap, uint8_t* outcome, uint64_t* info,
@@ -468,24 +465,19 @@ int emurx_launch_learn(const uint8_t* frames, const emurx_desc* desc, const emur
     using namespace emurx;
     unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
     if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 8 * (size_t)EMURX_LRN_INFO_WORDS, st)) ? 0 : -1;
-    const uint32_t nt = (n + kLrnTile - 1) / kLrnTile, mt = (max_frames + kLrnTile - 1) / kLrnTile;
-    uint8_t* p = static_cast<uint8_t*>(scratch);
-    uint4* slots = reinterpret_cast<uint4*>(p); p += (size_t)emurx_lrn_slots(max_frames) * 16;
-    uint32_t* slot_of = reinterpret_cast<uint32_t*>(p); p += lrn_align((size_t)max_frames * 4);
-    uint2* tsum = reinterpret_cast<uint2*>(p); p += lrn_align((size_t)mt * 8);
-    uint32_t* tcnt = reinterpret_cast<uint32_t*>(p); p += lrn_align((size_t)mt * 4);
-    uint32_t* tord = reinterpret_cast<uint32_t*>(p);
+    const uint32_t nt = (n + kLrnTile - 1) / kLrnTile;
+    const LrnScratch s = lrn_scratch(scratch, max_frames);  // sized by the handle's max_frames, not by n
     // the slots this batch probes: a power of two, at least twice its frames (never full), so a
     // small batch's keys stay within a few cache lines of a large handle's set
     const uint32_t mask = emurx_lrn_slots(n) - 1;
     const auto decide = (kinds & EMURX_LRNK_ND) ? k_lrn_decide<true> : k_lrn_decide<false>;
-    hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, slots, mask, slot_of,
-                                tsum, outcome);
-    if (e == hipSuccess) e = emurx_launch(k_lrn_mark, dim3(nt), dim3(kBlock), 0, st, slots, n, tsum, slot_of, tcnt);
+    hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, s.slots, mask,
+                                s.slot_of, s.tsum, outcome);
+    if (e == hipSuccess) e = emurx_launch(k_lrn_mark, dim3(nt), dim3(kBlock), 0, st, s.slots, n, s.tsum, s.slot_of, s.tcnt);
     if (e == hipSuccess)
-        e = emurx_launch(k_lrn_scan, dim3(1), dim3(kLrnScanBlock), 0, st, tsum, tcnt, nt, ev_cap, tord, inf);
+        e = emurx_launch(k_lrn_scan, dim3(1), dim3(kLrnScanBlock), 0, st, s.tsum, s.tcnt, nt, ev_cap, s.tord, inf);
     if (e == hipSuccess)
-        e = emurx_launch(k_lrn_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, slots, n, tsum, slot_of, tord, ev_cap, inf,
-                         reinterpret_cast<uint2*>(ev));
+        e = emurx_launch(k_lrn_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, s.slots, n, s.tsum, s.slot_of,
+                         s.tord, ev_cap, inf, reinterpret_cast<uint2*>(ev));
     return EMURX_HIP_OK(e) ? 0 : -1;
 }

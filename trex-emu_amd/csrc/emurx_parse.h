@@ -5,61 +5,18 @@
 // 583-959) and the per-callback Namespace / Client rules of src/emu/plugins/* as device
 // functions; the kernels that drive them are in emurx_kernels.hip.  The CPU oracle
 // (oracle/emurx_oracle.c) is the line-by-line twin the parity tests compare with.
+// The wave and workgroup primitives under it (lane_id, gld16, reductions, scans, the wave's
+// LDS hand-off) are in emurx_wave.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/emu_rx.h"
 #include "emurx_kernels.h"
 #include "emurx_tables.h"
+#include "emurx_wave.h"
 
 namespace emurx {
 
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / kWave;
-
-// loads through the global address space (global_load_*): pointers rebuilt from integers or
-// kept in a struct would otherwise compile to flat loads, which also count on lgkmcnt and
-// make the compiler serialise them with LDS traffic
-typedef unsigned emurx_v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 gld16(const void* p) {
-    const emurx_v4u v = *(const __attribute__((address_space(1))) emurx_v4u*)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-typedef unsigned emurx_v3u __attribute__((ext_vector_type(3)));
-__device__ __forceinline__ uint3 gld12(const void* p) {  // 4-byte aligned
-    const emurx_v3u v = *(const __attribute__((address_space(1))) emurx_v3u*)p;
-    return make_uint3(v.x, v.y, v.z);
-}
-__device__ __forceinline__ uint32_t gld4(const void* p) { return *(const __attribute__((address_space(1))) uint32_t*)p; }
-__device__ __forceinline__ uint32_t gld1(const void* p) { return *(const __attribute__((address_space(1))) uint8_t*)p; }
-
-// ---------------------------------------------------------------------------------------
-// wave helpers
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
-// wave64 reductions on the DPP network (quad perms, row rotates, row broadcasts; result is
-// read from lane 63 into a scalar register): no LDS traffic, 6 VALU + 1 readlane
-template <int kCtrl, int kRowMask = 0xf>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, kRowMask, 0xf, false);
-}
-template <class Op>
-__device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op) {
-    v = op(v, dpp<0xb1>(v));        // quad_perm [1,0,3,2]
-    v = op(v, dpp<0x4e>(v));        // quad_perm [2,3,0,1]
-    v = op(v, dpp<0x124>(v));       // row_ror:4
-    v = op(v, dpp<0x128>(v));       // row_ror:8
-    v = op(v, dpp<0x142, 0xa>(v));  // row_bcast:15
-    v = op(v, dpp<0x143, 0xc>(v));  // row_bcast:31
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    return wave_reduce(v, [](uint32_t x, uint32_t y) { return min(x, y); });
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    return wave_reduce(v, [](uint32_t x, uint32_t y) { return max(x, y); });
-}
 // Namespace-owner packing (emurx_route.hip, k_rx kind 2): the offset of `tile` in each owner's
 // region = its group's offset (grp_off, k_route_scan) + the counts of the group's earlier
 // tiles (tile_cnt[t][owner], 64 tiles per group).  Called by one whole wave; lane 0 writes
@@ -83,35 +40,20 @@ __device__ __forceinline__ TileOffLoads tile_offsets_issue(const uint32_t* tile_
     if (lane < parts) t.g = grp_off[(tile / 64) * 16 + lane];
     return t;
 }
-template <class R>
-__device__ __forceinline__ void tile_offsets_sum(const TileOffLoads& t, uint32_t parts, uint32_t lane, uint32_t* s_toff,
-                                                 R reduce_sum) {
+__device__ __forceinline__ void tile_offsets_sum(const TileOffLoads& t, uint32_t parts, uint32_t lane, uint32_t* s_toff) {
     const uint32_t c[EMURX_MAX_PARTS] = {t.x.x, t.x.y, t.x.z, t.x.w, t.y.x, t.y.y, t.y.z, t.y.w};
 #pragma unroll
     for (uint32_t k = 0; k < EMURX_MAX_PARTS; ++k) {
         if (k >= parts) break;
-        const uint32_t sum = reduce_sum(c[k]);
+        const uint32_t sum = wave_sum_u32(c[k]);
         const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)t.g, (int)k);
         if (lane == 0) s_toff[k] = g + sum;
     }
 }
-template <class R>
+// both steps at once (k_route<true>)
 __device__ __forceinline__ void tile_offsets(const uint32_t* tile_cnt, const uint32_t* grp_off, uint32_t parts,
-                                             uint32_t tile, uint32_t lane, uint32_t* s_toff, R reduce_sum) {
-    const uint32_t g0 = tile & ~63u;
-    uint4 x = make_uint4(0, 0, 0, 0), y = x;
-    if (g0 + lane < tile) {
-        const uint4* q = reinterpret_cast<const uint4*>(tile_cnt + (size_t)(g0 + lane) * 16);
-        x = q[0];
-        y = q[1];
-    }
-    const uint32_t c[EMURX_MAX_PARTS] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (uint32_t k = 0; k < EMURX_MAX_PARTS; ++k) {
-        if (k >= parts) break;
-        const uint32_t sum = reduce_sum(c[k]);
-        if (lane == 0) s_toff[k] = grp_off[(tile / 64) * 16 + k] + sum;
-    }
+                                             uint32_t tile, uint32_t lane, uint32_t* s_toff) {
+    tile_offsets_sum(tile_offsets_issue(tile_cnt, grp_off, parts, tile, lane), parts, lane, s_toff);
 }
 
 // The CTunnelKey VLAN words ParsePacket leaves for a frame (parser.go:801-818), from its
@@ -124,11 +66,6 @@ __device__ __forceinline__ void l2_vlans(uint32_t len, uint32_t w12, uint32_t w1
     const bool g1 = g0 && len >= 22 && (e1 == 0x8100 || e1 == 0x88A8);
     v0 = g0 ? (w12 & 0xffff0fffu) : 0u;
     v1 = g1 ? (w16 & 0xffff0fffu) : 0u;
-}
-
-// lanes below this one in mask m
-__device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -782,9 +719,6 @@ __device__ __forceinline__ void parse_flat(const LdsSrc& s, uint32_t len, uint32
 // best (2: +22 %, 8: +56 % on config E).
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kCoopVec = 4;
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    return wave_reduce(v, [](uint32_t x, uint32_t y) { return x + y; });
-}
 __device__ __forceinline__ void settle_deferred(Rec& r, bool ok) {
     if (ok) return;
     const uint32_t st = r.dfail & 0xffffu;
@@ -795,13 +729,6 @@ __device__ __forceinline__ void settle_deferred(Rec& r, bool ok) {
 __device__ __forceinline__ uint32_t span_sum(const uint4& x, uint32_t nv, int h, int t, uint32_t k) {
     if (k >= nv) return 0;
     return sad_vec_masked(x, k == 0 ? h : 0, k == nv - 1 ? t : 16, 0);
-}
-__device__ __forceinline__ uint32_t dpp_row_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
-    return v;  // lane 15 of each row: the row's total
 }
 #ifndef EMURX_COOP_NT
 #define EMURX_COOP_NT 0
@@ -819,12 +746,8 @@ __device__ __forceinline__ uint32_t coop_span_sum(const uint8_t* span, uint32_t 
     const uint32_t nv = mine ? (uint32_t)((((e + 15) & ~(uintptr_t)15) - (a & ~(uintptr_t)15)) >> 4) : 0u;
     const uint32_t rounds = (nv + kRound - 1) / kRound;
     uint32_t incl = rounds;
-#pragma unroll
-    for (uint32_t o = 1; o < kWave; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += up;
-    }
-    const uint32_t R = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
+    wave_incl_scan(incl);
+    const uint32_t R = wave_last(incl);
     // row of this lane's span: its rounds' midpoint in the wave's total, in quarters
     const uint32_t g = mine ? min(3u, (uint32_t)(((uint64_t)(2 * incl - rounds) * 4) / (2 * (uint64_t)R))) : 4u;
     uint64_t rm = 0;  // the spans of this lane's row (lanes in order)
@@ -872,9 +795,7 @@ __device__ __forceinline__ uint32_t coop_span_sum(const uint8_t* span, uint32_t 
             j = rest ? (uint32_t)__ffsll((long long)rest) - 1 : 64u;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     return mine ? wsum[lane] : 0u;
 }
 // the rx window path's deferred L4 checksums (r.dstart / r.dlen of each lane's frame f)

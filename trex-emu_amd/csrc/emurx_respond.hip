@@ -176,33 +176,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     if ((s_sum[0] & 0x3ffu) && i < n) plan[i] = p.outcome << 16 | p.len;
 }
 
-// inclusive scan over a workgroup of kRspScanBlock lanes (s_w: one word pair per wave)
-__device__ __forceinline__ void rsp_block_scan(uint32_t& c, unsigned long long& r, uint32_t (*s_c)[2],
-                                               unsigned long long* s_r) {
-    const uint32_t lane = lane_id(), wv = threadIdx.x / kWave, nw = blockDim.x / kWave;
-#pragma unroll
-    for (uint32_t d = 1; d < kWave; d <<= 1) {
-        const uint32_t uc = (uint32_t)__shfl_up((int)c, d);
-        const unsigned long long ur = __shfl_up(r, d);
-        if (lane >= d) {
-            c += uc;
-            r += ur;
-        }
-    }
-    __syncthreads();  // the previous round's readers
-    if (lane == kWave - 1) {
-        s_c[wv][0] = c;
-        s_r[wv] = r;
-    }
-    __syncthreads();
-    for (uint32_t w = 0; w < nw; ++w) {
-        if (w < wv) {
-            c += s_c[w][0];
-            r += s_r[w];
-        }
-    }
-}
-
 // info: {n_out, bytes needed, count of outcomes 1..7, zeros}, info_words (8 or
 // EMURX_RSP_INFO_WORDS) of them: the scan writes bytes needed, DROP_MCAST and HOST and zeroes the
 // rest; the emit pass adds n_out, the replies by kind and NOSPC
@@ -210,11 +183,12 @@ __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restr
                                                             uint32_t* __restrict__ tord,
                                                             unsigned long long* __restrict__ trow,
                                                             unsigned long long* __restrict__ info, uint32_t info_words) {
-    __shared__ uint32_t s_c[kRspScanBlock / kWave][2];
-    __shared__ unsigned long long s_r[kRspScanBlock / kWave];
+    __shared__ BlockScanLds<kRspScanBlock, uint32_t, unsigned long long> s_scan;
     __shared__ uint32_t s_dh[2];
     if (threadIdx.x < 2) s_dh[threadIdx.x] = 0;
     uint32_t cbase = 0, drop = 0, host = 0;
+    // rows are counted in 64 bits (r, the round's total and rbase): a batch of fewer than 2^26
+    // jumbo echo requests (576 rows each) can hold more than 2^32 of them
     unsigned long long rbase = 0;
     for (uint32_t t0 = 0; t0 < ntiles; t0 += kRspScanBlock) {  // workgroup-uniform trip count
         const uint32_t t = t0 + threadIdx.x;
@@ -224,19 +198,13 @@ __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restr
         host += v.x >> 20;
         uint32_t c = cnt;
         unsigned long long r = v.y;
-        rsp_block_scan(c, r, s_c, s_r);
+        const auto [ctot, rtot] = block_incl_scan<kRspScanBlock>(s_scan, c, r);
         if (t < ntiles) {
             tord[t] = cbase + c - cnt;
             trow[t] = rbase + r - v.y;
         }
-        __syncthreads();
-        if (threadIdx.x == kRspScanBlock - 1) {
-            s_c[0][1] = c;
-            s_r[0] = r;
-        }
-        __syncthreads();
-        cbase += s_c[0][1];
-        rbase += s_r[0];
+        cbase += ctot;
+        rbase += rtot;
     }
     drop = wave_sum_u32(drop);
     host = wave_sum_u32(host);
@@ -287,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
                                                      uint8_t* __restrict__ out, unsigned long long cap,
                                                      emurx_desc* __restrict__ odesc, uint32_t* __restrict__ osrc,
                                                      uint8_t* __restrict__ outcome, unsigned long long* __restrict__ info) {
-    __shared__ uint32_t s_w[kWaves][2];
+    __shared__ BlockScanLds<kBlock, uint32_t, uint32_t> s_scan;
     __shared__ uint32_t s_row[kRspTile + 1];  // first row (in the tile) of reply k; [replies] = the tile's rows
     __shared__ RspReply s_rep[kRspTile];
     __shared__ uint32_t s_mac[kRspTile][3];   // an echo reply's first 12 bytes: the Ethernet addresses swapped
@@ -297,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
     const uint2 ts = tsum[t];
     const uint32_t replies = ts.x & 0x3ffu;
     if (!replies) return;  // workgroup-uniform
-    const uint32_t lane = lane_id(), wv = threadIdx.x / kWave, i = t * kRspTile + threadIdx.x;
+    const uint32_t i = t * kRspTile + threadIdx.x;
     if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
     const uint32_t ord0 = tord[t];
     const unsigned long long row0 = trow[t];
@@ -305,25 +273,9 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
     const uint32_t kind = p >> 16, rlen = p & 0xffffu;
     const bool reply = rsp_is_reply(kind);
     const uint32_t rows = reply ? (rlen + 15) >> 4 : 0u;
-    // ordinal and first row inside the tile: wave scans, then the waves' totals
+    // ordinal and first row inside the tile (the one scan of this launch: kAgain = false)
     uint32_t k = reply ? 1u : 0u, r = rows;
-#pragma unroll
-    for (uint32_t d = 1; d < kWave; d <<= 1) {
-        const uint32_t uk = (uint32_t)__shfl_up((int)k, d), ur = (uint32_t)__shfl_up((int)r, d);
-        if (lane >= d) {
-            k += uk;
-            r += ur;
-        }
-    }
-    if (lane == kWave - 1) {
-        s_w[wv][0] = k;
-        s_w[wv][1] = r;
-    }
-    __syncthreads();
-    for (uint32_t w = 0; w < wv; ++w) {
-        k += s_w[w][0];
-        r += s_w[w][1];
-    }
+    block_incl_scan<kBlock, false>(s_scan, k, r);
     k -= reply ? 1u : 0u;
     r -= rows;
     if (threadIdx.x == 0) s_row[replies] = ts.y;
@@ -545,11 +497,19 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
 }  // namespace emurx
 
 // scratch: plan u32 [n], tile sums uint2 [ntiles], tile ordinals u32 [ntiles], tile rows u64 [ntiles]
-static size_t rsp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t emurx_rsp_scratch_bytes(uint32_t n) {
-    const size_t nt = (n + emurx::kRspTile - 1) / emurx::kRspTile;
-    return rsp_align((size_t)n * 4) + rsp_align(nt * 8) + rsp_align(nt * 4) + rsp_align(nt * 8);
+struct RspScratch {
+    uint32_t* plan;
+    uint2* tsum;
+    uint32_t* tord;
+    unsigned long long* trow;
+    size_t bytes;
+};
+static RspScratch rsp_scratch(void* base, uint32_t n) {
+    const size_t nt = ((size_t)n + emurx::kRspTile - 1) / emurx::kRspTile;
+    emurx_carver c(base);  // the initialisers run in order
+    return {c.take<uint32_t>(n), c.take<uint2>(nt), c.take<uint32_t>(nt), c.take<unsigned long long>(nt), c.bytes()};
 }
+size_t emurx_rsp_scratch_bytes(uint32_t n) { return rsp_scratch(nullptr, n).bytes; }
 
 int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
                          uint32_t kinds, const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc,
@@ -559,17 +519,14 @@ int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const em
     unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
     if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 8 * (size_t)info_words, st)) ? 0 : -1;
     const uint32_t nt = (n + kRspTile - 1) / kRspTile;
-    uint8_t* p = static_cast<uint8_t*>(scratch);
-    uint32_t* plan = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)n * 4);
-    uint2* tsum = reinterpret_cast<uint2*>(p); p += rsp_align((size_t)nt * 8);
-    uint32_t* tord = reinterpret_cast<uint32_t*>(p); p += rsp_align((size_t)nt * 4);
-    unsigned long long* trow = reinterpret_cast<unsigned long long*>(p);
+    const RspScratch s = rsp_scratch(scratch, n);
     const auto decide = (kinds & EMURX_RSPK_ND) ? k_rsp_decide<true> : k_rsp_decide<false>;
-    hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, plan, tsum, outcome);
+    hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, s.plan, s.tsum,
+                                outcome);
     if (e == hipSuccess)
-        e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, tsum, nt, tord, trow, inf, info_words);
+        e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, s.tsum, nt, s.tord, s.trow, inf, info_words);
     if (e == hipSuccess)
-        e = emurx_launch(k_rsp_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, plan, tsum, tord, trow, out,
-                         (unsigned long long)cap, out_desc, out_src, outcome, inf);
+        e = emurx_launch(k_rsp_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, s.plan, s.tsum, s.tord,
+                         s.trow, out, (unsigned long long)cap, out_desc, out_src, outcome, inf);
     return EMURX_HIP_OK(e) ? 0 : -1;
 }

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void k_route(const emurx_rec* __restrict__ 
     // {ns, client, vlan0, vlan1} {vport | l3 << 16, ...}
     const uint32_t d = a.x != EMURX_ID_NONE ? emurx_owner(emurx_tk_hash(b.x & 0xffffu, a.z, a.w), n_parts) : 0xffu;
     if (kPack && wv == 0)  // this tile's offset: group offset + the group's earlier tiles
-        tile_offsets(tile_cnt, grp_off, n_parts, tile, lane, s_toff, [](uint32_t v) { return wave_sum_u32(v); });
+        tile_offsets(tile_cnt, grp_off, n_parts, tile, lane, s_toff);
     uint32_t rank = 0;
     uint64_t left = __ballot(d != 0xffu);
     while (left) {
@@ -82,9 +82,7 @@ __global__ __launch_bounds__(kBlock) void k_route(const emurx_rec* __restrict__ 
     park[lane * 5 + 2] = make_uint2(b.x, b.y);
     park[lane * 5 + 3] = make_uint2(b.z, b.w);
     park[lane * 5 + 4] = make_uint2(i, my_rank);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for (uint32_t k = 0; k < 5; ++k) {
         const uint32_t p = k * kWave + lane, rr = p / 5, part = p - rr * 5;
@@ -117,11 +115,7 @@ __global__ __launch_bounds__(kScanThreads) void k_route_scan(uint32_t* __restric
         const uint32_t v = k == 0 ? x.x : k == 1 ? x.y : k == 2 ? x.z : k == 3 ? x.w
                          : k == 4 ? y.x : k == 5 ? y.y : k == 6 ? y.z : y.w;
         uint32_t incl = v;
-#pragma unroll
-        for (uint32_t o = 1; o < kWave; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-            if (lane >= o) incl += up;
-        }
+        wave_incl_scan(incl);
         if (lane == kWave - 1) s_wsum[k][wv] = incl;
         s_ex[k][t] = incl - v;
     }
@@ -207,10 +201,8 @@ __global__ __launch_bounds__(kBlock) void k_owner_count(const uint8_t* __restric
                 if (j * kWave < nvec)
                     __builtin_amdgcn_global_load_lds(src + min(lane + j * kWave, nvec - 1),
                                                      (__attribute__((address_space(3))) void*)(dst + j * kWave), 16, 0, 2);
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the wave's DMA landed
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wait_vm0();  // vmcnt(0): the wave's DMA landed
+            wave_lds_sync();
         }
         uint32_t d = keyed ? emurx_owner_of_key(pad, n_parts) : 0xffu;
         if (need) {
@@ -364,10 +356,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMURX_LO
             __builtin_amdgcn_global_load_lds(base + k * kWave + lane,
                                              (__attribute__((address_space(3))) void*)&s_rec[wv][k * kWave], 16, 0,
                                              EMURX_LOOKUP_NT ? 2 : 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wait_vm0();
+    wave_lds_sync();
     const bool live = idx < cnt;
     const uint4 q0 = s_rec[wv][lane * 2], q1 = s_rec[wv][lane * 2 + 1];
     const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -407,9 +397,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMURX_LO
         park[lane * 5 + 3] = make_uint2(r.l7len | (r.nh << 16) | (r.proto << 24), r.status | (r.flags << 8));
         park[lane * 5 + 4] = make_uint2(w[0], src);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     uint2* o = reinterpret_cast<uint2*>(out + (uint64_t)src * cap + idx0);  // 8-B aligned
     const uint32_t npieces = min(kWave, cnt - idx0) * 5;
 #pragma unroll

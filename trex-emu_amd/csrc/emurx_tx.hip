@@ -176,10 +176,8 @@ __global__ __launch_bounds__(kBlock) void k_tx_csum(uint8_t* __restrict__ frames
             if (k * kWave < nvec)
                 __builtin_amdgcn_global_load_lds(src + min(lane + k * kWave, nvec - 1),
                                                  (__attribute__((address_space(3))) void*)(dst + k * kWave), 16, 0, 0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the wave's rows landed
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wait_vm0();  // vmcnt(0): the wave's rows landed
+        wave_lds_sync();
         const TxLds s{reinterpret_cast<const uint8_t*>(s_slab[wv]), s_slab[wv], d.x - lo + skew};
         ok = live && tx_sums(s, len, l3, l4, osize, ops, nhx, hcs, lcs, fo);
     } else {
@@ -198,10 +196,8 @@ __global__ __launch_bounds__(kBlock) void k_tx_csum(uint8_t* __restrict__ frames
                                                  0);
         const bool want = live && (ops >> EMURX_TX_L4_SHIFT) != 0 && l4 < len;
         const uint32_t pre = coop_span_sum(frames + d.x + l4, want ? len - l4 : 0u, want, s_wsum[wv]);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the windows landed
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wait_vm0();  // vmcnt(0): the windows landed
+        wave_lds_sync();
         const WinSrc w{reinterpret_cast<const uint8_t*>(s_slab[wv]), s_slab[wv], lane * 16, head,
                        min(kTxWinVec * 16 - head, len), frames + d.x};
         ok = live && tx_sums(TxWinPre{w, l4, want ? len - l4 : 0u, pre}, len, l3, l4, osize, ops, nhx, hcs, lcs, fo);

@@ -23,22 +23,12 @@
 
 #include "../../include/emu_rx.h"
 #include "emurx_kernels.h"
-#include "emurx_parse.h"
+#include "emurx_wave.h"
 
 namespace emurx {
 
 constexpr uint32_t kTxTile = 64;  // frames per wave; == EMURX_ZMQ_TX_BURST
 static_assert(kTxTile == EMURX_ZMQ_TX_BURST && kTxTile == kWave, "one burst per wave");
-
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < kWave; d <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 #ifndef EMURX_TXC_NOUP
 #define EMURX_TXC_NOUP 0
@@ -46,13 +36,12 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
 // end(i) - i for lane i of the tile at `base`, from this tile's and the next tile's lengths
 __device__ __forceinline__ uint32_t tx_endrel_v(uint32_t len, uint32_t lb, uint32_t n, uint32_t base, uint32_t* q) {
     const uint32_t lane = lane_id();
-    const uint32_t qa = wave_incl_scan_u32(len);
-    const uint32_t qb = wave_incl_scan_u32(lb) + (uint32_t)__shfl((int)qa, kWave - 1);
+    uint32_t qa = len, qb = lb;
+    wave_incl_scan(qa, qb);
+    qb += wave_last(qa);
     q[lane] = qa;
     q[kWave + lane] = qb;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const uint32_t thr = qa - len + EMURX_ZMQ_TX_MAX_BUFFER;
     uint32_t lo = lane + 1, hi = lane + kTxTile;
 #pragma unroll
@@ -113,11 +102,6 @@ struct TxChainLds {
     uint32_t fbw[kTxUnitWaves][2];  // the size feedback's per-wave bounds
     uint32_t last;
 };
-__device__ __forceinline__ void tx_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // The hand-off between the workgroup that composes a unit and the one that composes its parent
 // (MI355X_MICROARCH.md's hand-off table, row 1): T and B stored write-through (sc1), every
 // storing wave waits for its stores, a workgroup barrier, one agent-scope atomic add per
@@ -165,11 +149,7 @@ __device__ void tx_compose_table(const TxChain& c, uint32_t k, uint32_t p, uint3
     } else if (wv == 1) {  // bytes before each child, the unit's bytes
         const unsigned long long b = lane < cn ? S.b[lane] : 0ull;
         unsigned long long s = b;
-#pragma unroll
-        for (uint32_t d = 1; d < kWave; d <<= 1) {
-            const unsigned long long u = __shfl_up(s, d);
-            if (lane >= d) s += u;
-        }
+        wave_incl_scan(s);
         c.RB[k][(size_t)p * 64 + lane] = s - b;
         if (lane == kWave - 1) __hip_atomic_store(&c.B[k][p], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -218,11 +198,12 @@ __global__ __launch_bounds__(kTxUnitWaves * kWave) void k_txz_chain(const emurx_
     uint32_t carry = 0;
 #pragma unroll
     for (uint32_t j = 0; j <= kTxTilesPerWave; ++j) {
-        const uint32_t s = wave_incl_scan_u32(len[j]) + carry;
-        q[j * kWave + lane] = s;
-        carry = (uint32_t)__shfl((int)s, kWave - 1);
+        uint32_t s = len[j];
+        wave_incl_scan(s);
+        q[j * kWave + lane] = s + carry;
+        carry += wave_last(s);
     }
-    tx_wave_sync();
+    wave_lds_sync();
     const uint32_t limw = n > wbase ? n - wbase : 0u;  // frames from this wave's base on
     uint32_t* er = S.u.leaf.er[wv];
 #pragma unroll
@@ -239,7 +220,7 @@ __global__ __launch_bounds__(kTxUnitWaves * kWave) void k_txz_chain(const emurx_
         }
         er[g] = g < limw ? min(lo, limw) - g : 0u;
     }
-    tx_wave_sync();
+    wave_lds_sync();
     // per tile and entry e (lane): the messages started inside and the exit offset
     uint32_t s[kTxTilesPerWave], m[kTxTilesPerWave], lim[kTxTilesPerWave];
 #pragma unroll
@@ -408,7 +389,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
         starts |= 1ull << s;
     const uint32_t upto = (uint32_t)__popcll(starts & ((lane == 63) ? ~0ull : ((2ull << lane) - 1)));
     const uint32_t msg = tmb + upto - 1;  // upto == 0: the previous tile's last message
-    const uint32_t pre = wave_incl_scan_u32(len) - len;
+    uint32_t pre = len;
+    wave_incl_scan(pre);
+    pre -= len;
     const unsigned long long fo = 4ull * (msg + 1ull) + 4ull * (base + lane) + tbb + pre;
     const bool st = valid && ((starts >> lane) & 1);  // this frame opens a message
     if (st) msg_off[msg] = fo - 4;
@@ -426,7 +409,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
     if (kTxImg && nrow * 16 <= kTxImg) {  // wave-uniform: the tile's output rows fit the image
 
         for (uint32_t r = lane; r < nrow; r += kWave) reinterpret_cast<uint4*>(o32)[r] = make_uint4(0, 0, 0, 0);
-        tx_wave_sync();
+        wave_lds_sync();
         if (valid) {
             const uint32_t p = (uint32_t)(fo - obase);  // the frame header in the image
             if (st) lds_or4(o32, p - 4, __builtin_bswap32(((uint32_t)EMURX_ZMQ_MAGIC << 16) + er));
@@ -467,7 +450,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
                 }
             }
         }
-        tx_wave_sync();
+        wave_lds_sync();
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         for (uint32_t r = lane; r < nrow; r += kWave) {
             const unsigned long long x = obase + 16ull * r;
@@ -502,7 +485,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
         sg[4][lane] = ((uint32_t)EMURX_ZMQ_PKT_MAGIC << 24) + ((uint32_t)dl.vport << 16) + dl.len;
         sg[5][lane] = st ? ((uint32_t)EMURX_ZMQ_MAGIC << 16) + er : 0u;
     }
-    tx_wave_sync();
+    wave_lds_sync();
     const uint32_t head = (uint32_t)(o0 & 15);  // nrow (above) = (head + R + 15) / 16
     const unsigned long long xb = o0 - head;  // 16-byte aligned (d_out is)
     auto byte_at = [&](uint32_t y, uint32_t kk) {  // output byte y of the tile (y < R), segment >= kk
@@ -606,7 +589,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
 #if EMURX_TX_P2ROUND && !defined(EMURX_TX_NOPASS2)
         // this round's byte-by-byte rows now, while the lines its full rows wrote are in L2 (a
         // line left partly written costs its write-back a read-modify-write)
-        tx_wave_sync();
+        wave_lds_sync();
         const uint32_t nl = min(nslow, kTxSlow);
         for (uint32_t i = p2done * 16 + lane; i < nl * 16; i += kWave) {
             const uint32_t e = slow[i >> 4];
@@ -615,7 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
         p2done = nl;
 #endif
     }
-    tx_wave_sync();
+    wave_lds_sync();
 #ifdef EMURX_TX_NOPASS2  // timing only: the long path without its byte-by-byte rows (wrong output)
     const uint32_t nb = 0;
 #else

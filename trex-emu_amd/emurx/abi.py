@@ -301,7 +301,7 @@ def source_id() -> str | None:
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
            "emurx_respond.hip", "emurx_learn.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
-    hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
+    hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()
     try:
