@@ -763,6 +763,122 @@ int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_des
                     emurx_learn_ev* d_ev, uint32_t ev_cap,
                     uint8_t* d_outcome, uint64_t* d_info, void* stream);
 
+/* ---- the handlers' per-Namespace counters, folded per batch ---------------------------------
+   The ARP, ICMPv4 and ICMPv6 / ND handlers count per Namespace (ArpNsStats plugins/arp/arp.go:797,
+   IcmpNsStats plugins/icmp/icmp.go:255, the ipv6 and nd stats of PluginIpv6Ns).  For a frame the
+   responder has answered and the learning fold has folded, the counters are all that is left of
+   its handler.  emurx_nsstat_dev decides per frame whether the Go handler still has to run
+   (d_done) and folds the counters of the frames whose handler does not into one event per
+   Namespace.  d_rec: the records emurx_classify_dev wrote for d_frames / d_desc on this handle
+   (records of emurx_lookup_dev from another GPU are out of scope: their frames are elsewhere).
+   kinds: EMURX_RSPK_* bits.  d_rsp_outcome: the outcome array of an emurx_respond_kinds_dev call
+   on the same batch and records with at least these kinds.  d_lrn_outcome: that of an
+   emurx_learn_dev call with ARP and / or ND as selected here; read only when kinds has
+   EMURX_RSPK_ARP or EMURX_RSPK_ND (else it may be NULL).  If that learn call overflowed, repeat it
+   with a larger ev_cap before trusting d_done for frames with learn outcome 1..4.
+   d_done[i] (may be NULL):
+     0  the Go handler runs as today and counts itself; the frame contributes nothing here
+     1  everything the handler would do besides the reply and the learning is in this call's
+        counters: skip the handler (every such handler returns 0)
+     2  the handler would only return PARSER_ERR: lookup EMURX_LK_NO_NS or EMURX_LK_NS_NO_PLUGIN
+        (arp.go:958-965, icmp.go:486-493, ipv6.go:546-553); add d_info[4] to errParser and skip it
+   A frame is a candidate if rec.status == EMURX_ST_OK, its descriptor is no hole and its callback
+   is one `kinds` selects (arp: ARP; icmp: ICMP; icmpv6: ICMPV6 or ND); every other frame gets 0.
+   A candidate with lookup NO_NS / NS_NO_PLUGIN gets 2, one with EMURX_LK_NONE 0.  Then, before any
+   byte of the frame is read, the header offsets (the responder's and the learner's tests): arp
+   l3 < 14 or l3 + 28 > len; icmp l3 < 14, l3 + 20 > len or l4 + 8 > len; icmpv6 l3 < 14, l3 + 40 >
+   l4 or l4 + 4 > len: each gives 0.  So does a record whose ns_id is not below cfg.max_ns (and
+   2^27).  Then (idx: enum emurx_nsc below; paths relative to src/emu/plugins):
+     arp     learn outcome EMURX_LRN_HOST -> 0.  Operation p[l3+6:l3+8] (arp.go:914-945):
+             1: pktRxArpQuery (:916); lookup NO_CLIENT: also pktRxArpQueryNotForUs (:932), done 1;
+                CLIENT_NO_PLUGIN: done 1 (:926-927); CLIENT with responder outcome EMURX_RSP_ARP:
+                also pktTxReply (Respond :778), done 1; CLIENT with any other responder outcome
+                (HOST, NOSPC, NONE): done 0 and no counter at all; lookup NS_LEVEL (no classify
+                gives it to a request): done 0.
+             2: Ethernet destination ff:ff:ff:ff:ff:ff: pktRxErrNoBroadcast (:937), else
+                pktRxArpReply (:940); done 1.    any other: pktRxErrWrongOp (:944), done 1.
+     icmp    HandleRxIcmpPacket icmp.go:396-462; the classifier has done CLookupByIPv4(dst) and
+             IsUnicastToMe (:417-427), NO_CLIENT where either fails.  NO_CLIENT:
+             pktRxNoClientUnhandled (:419, :425), done 1.  CLIENT: responder outcome DROP_MCAST:
+             pktRxErrMulticastB (:434, HandleEcho :296), done 1; EMURX_RSP_ICMP: pktRxIcmpQuery and
+             pktTxIcmpResponse (:322-323; one word, EMURX_NSC_ICMP_ECHO), done 1; else type, code
+             p[l4], p[l4+1] (gopacket layers/icmp4.go:20-43): (8,0) echo request (a reply that
+             did not fit, a kind the responder did not build), (13,0) timestamp request, (0,0) echo
+             reply, (3, 0..4) destination unreachable Net / Host / Protocol / Port /
+             FragmentationNeeded (:438-456): done 0; every other type / code: pktRxErrUnhandled
+             (:458), done 1.  Any other lookup: done 0.
+     icmpv6  HandleRxIpv6Packet ipv6/ipv6.go:465-539; type, code p[l4], p[l4+1] (gopacket
+             layers/icmp6.go:21-52).
+             (128,0) echo request, with EMURX_RSPK_ICMPV6: NO_CLIENT with IPv6 source byte p[l3+8] ==
+             0xff: done 0 (the classifier folds the source test of :499 into NO_CLIENT, so the
+             record cannot tell pktRxErrMulticastB from pktRxNoClientUnhandled); NO_CLIENT otherwise:
+             pktRxNoClientUnhandled (:488, :494), done 1; CLIENT: responder EMURX_RSP_ICMPV6:
+             pktRxIcmpQuery and pktTxIcmpResponse (:354-355; one word), done 1; DROP_MCAST:
+             pktRxErrMulticastB (:322), done 1; else done 0.
+             Every other type needs lookup NS_LEVEL (else done 0).
+             (135,0) neighbour solicitation, with EMURX_RSPK_ND: responder outcome EMURX_RSP_ND and
+             learn outcome NONE or ND_NS: pktRxNeighborSolicitation (nd.go:1547) and, if the IPv6
+             source is unspecified (the responder's predicate, IPv4-mapped reading included),
+             pktTxNeighborDADError (:1240), else pktTxNeighborAdvUnicast (:1246); done 1.  Any other
+             combination: done 0 (every unanswered solicitation has a rejection counter of its
+             own, which stays with Go).
+             (136,0) neighbour advertisement, with EMURX_RSPK_ND: learn outcome ND_NA:
+             pktRxNeighborAdvertisement (:1688) and pktRxNeighborAdvLearn (:1758, :1768), done 1;
+             else done 0.
+             done 0: (130..132,0) and (143,0) MLD (:505-509), (133,0), (134,0), (137,0) router
+             solicitation, router advertisement, redirect (:511-516), (129,0) echo reply (:517),
+             (1, 0..6) destination unreachable (:522-528).
+             Every other type / code the parser lets through, with EMURX_RSPK_ICMPV6:
+             pktRxErrUnhandled (:535), done 1.
+   Output: one event per Namespace that has a frame with done 1, in ascending ns_id (fully
+   determined).  d_info (u64[EMURX_NSS_INFO_WORDS]) = {events written, distinct Namespaces,
+   overflow (0 or 1), frames with done 1, frames with done 2, candidates left at done 0, 0, 0}.
+   Overflow is distinct Namespaces > ev_cap and nothing else: then d_info[0] is 0 and nothing is
+   written to d_ev, while d_done and the rest of d_info stay valid.  Nothing is ever written at or
+   past d_ev[ev_cap].  kinds == 0 or a bit above EMURX_RSPK_ALL, ev_cap == 0 or ev_cap >
+   emurx_nsstat_max_events(h) (= min(cfg.max_frames, cfg.max_ns)), a NULL d_ev or d_info, with
+   n > 0 a NULL d_frames, d_desc, d_rec, d_rsp_outcome or (kinds with ARP or ND) d_lrn_outcome, and
+   a capturing stream are EMURX_EINVAL; n > cfg.max_frames is EMURX_ENOMEM; a host-only handle
+   EMURX_EDEVICE.  d_rec 16-byte aligned, d_desc, d_ev and d_info 8-byte.  n == 0 writes a zero
+   d_info.  Three launches on `stream` (decide + fold, scan, emit), no host synchronisation and no
+   allocation (the scratch is sized at emurx_open from max_frames and max_ns), behind the table
+   shipment emurx_classify_dev describes; calls on different streams of one handle share the
+   scratch, so they must not overlap.  INTEGRATION.md has the replay loop and the dispatch rule. */
+enum emurx_nsc {                 /* index into emurx_nsstat_ev.cnt */
+    EMURX_NSC_ARP_QUERY = 0,            /* ArpNsStats.pktRxArpQuery            */
+    EMURX_NSC_ARP_QUERY_NOT_FOR_US = 1, /* pktRxArpQueryNotForUs               */
+    EMURX_NSC_ARP_REPLY = 2,            /* pktRxArpReply                       */
+    EMURX_NSC_ARP_ERR_NO_BROADCAST = 3, /* pktRxErrNoBroadcast                 */
+    EMURX_NSC_ARP_ERR_WRONG_OP = 4,     /* pktRxErrWrongOp                     */
+    EMURX_NSC_ARP_TX_REPLY = 5,         /* pktTxReply                          */
+    EMURX_NSC_ICMP_ECHO = 6,            /* IcmpNsStats.pktRxIcmpQuery and pktTxIcmpResponse */
+    EMURX_NSC_ICMP_NO_CLIENT = 7,       /* pktRxNoClientUnhandled              */
+    EMURX_NSC_ICMP_ERR_MCAST = 8,       /* pktRxErrMulticastB                  */
+    EMURX_NSC_ICMP_ERR_UNHANDLED = 9,   /* pktRxErrUnhandled                   */
+    EMURX_NSC_V6_ECHO = 10,             /* ipv6 pktRxIcmpQuery and pktTxIcmpResponse */
+    EMURX_NSC_V6_NO_CLIENT = 11,        /* ipv6 pktRxNoClientUnhandled         */
+    EMURX_NSC_V6_ERR_MCAST = 12,        /* ipv6 pktRxErrMulticastB             */
+    EMURX_NSC_V6_ERR_UNHANDLED = 13,    /* ipv6 pktRxErrUnhandled              */
+    EMURX_NSC_ND_RX_NS = 14,            /* nd pktRxNeighborSolicitation        */
+    EMURX_NSC_ND_TX_ADV_UNICAST = 15,   /* pktTxNeighborAdvUnicast             */
+    EMURX_NSC_ND_TX_DAD_ERROR = 16,     /* pktTxNeighborDADError               */
+    EMURX_NSC_ND_RX_NA = 17,            /* pktRxNeighborAdvertisement          */
+    EMURX_NSC_ND_RX_NA_LEARN = 18       /* pktRxNeighborAdvLearn; 19..21 zero  */
+};
+#define EMURX_NSC_WORDS 22
+#define EMURX_NSS_INFO_WORDS 8
+typedef struct emurx_nsstat_ev {
+    uint32_t ns_id;                  /* rec.ns_id of the frames folded                         */
+    uint32_t frames;                 /* frames with done == 1 folded into this event (>= 1)    */
+    uint32_t cnt[EMURX_NSC_WORDS];   /* enum emurx_nsc; unused words 0                         */
+} emurx_nsstat_ev;                   /* 96 bytes */
+uint32_t emurx_nsstat_max_events(const emurx_t* h);   /* min(cfg.max_frames, cfg.max_ns) */
+int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                     const emurx_rec* d_rec, uint32_t n, uint32_t kinds,
+                     const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome,
+                     emurx_nsstat_ev* d_ev, uint32_t ev_cap,
+                     uint8_t* d_done, uint64_t* d_info, void* stream);
+
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);
 /* Sum the EMURX_HIST_SHARDS copies of a device histogram (after a D2H copy). */

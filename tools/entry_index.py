@@ -54,6 +54,9 @@ GROUPS = [
      "`NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
     ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events", "emurx_learn_key_hash"],
      "`PluginArpNs.ArpLearn` `arp/arp.go:886-901`, `NdLearn` `ipv6/nd.go:1611-1620`, `:1687-1776`"),
+    ("Device handler counters", ["emurx_nsstat_dev", "emurx_nsstat_max_events"],
+     "the counters of `HandleRxArpPacket` `arp/arp.go:904-946`, `HandleRxIcmpPacket` `icmp/icmp.go:396-462`, "
+     "`HandleRxIpv6Packet` `ipv6/ipv6.go:465-539`, `HandleRxIpv6NdPacket` `ipv6/nd.go:1546-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_uniform", "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

@@ -196,6 +196,10 @@ struct emurx_ctx {
     // set is zero between calls; a call whose launches failed half way leaves it to be cleared
     DevBuf<uint8_t> d_lrn;
     bool lrn_dirty = false;
+    // the per-Namespace counter fold's scratch (emurx_nsstat_dev), sized at emurx_open from max_frames
+    // and max_ns: its accumulator rows and flags are zero between calls, cleared like the learning set
+    DevBuf<uint8_t> d_nss;
+    bool nss_dirty = false;
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -864,6 +868,11 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
         emurx_close(h);
         return EMURX_ENOMEM;
     }
+    if (h->d_nss.alloc(emurx_nss_scratch_bytes(cfg->max_frames, cfg->max_ns)) ||
+        !EMURX_HIP_OK(hipMemset(h->d_nss.p, 0, emurx_nss_scratch_bytes(cfg->max_frames, cfg->max_ns)))) {
+        emurx_close(h);
+        return EMURX_ENOMEM;
+    }
     emurx_t::RouteScratch* rs = nullptr;
     if ((rc = ship_tables(h, h->stream)) || (rc = route_scratch(h, cfg->max_frames, h->stream, &rs)) == EMURX_ENOMEM) {
         emurx_close(h);
@@ -899,6 +908,7 @@ void emurx_close(emurx_t* h) {
     h->d_txz.release();
     h->d_rsp.release();
     h->d_lrn.release();
+    h->d_nss.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
     for (auto& e : h->ev)
@@ -1487,6 +1497,36 @@ int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_des
     if (emurx_launch_learn(d_frames, d_desc, d_rec, n, kinds, h->tables(), d_ev, ev_cap, d_outcome, d_info, h->d_lrn.p,
                            h->cfg.max_frames, st)) {
         h->lrn_dirty = true;
+        return EMURX_EDEVICE;
+    }
+    return EMURX_OK;
+}
+
+uint32_t emurx_nsstat_max_events(const emurx_t* h) { return h ? std::min(h->cfg.max_frames, h->cfg.max_ns) : 0; }
+
+int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                     uint32_t kinds, const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome, emurx_nsstat_ev* d_ev,
+                     uint32_t ev_cap, uint8_t* d_done, uint64_t* d_info, void* stream) {
+    if (!h || !d_info || !d_ev || (n && (!d_frames || !d_desc || !d_rec || !d_rsp_outcome))) return EMURX_EINVAL;
+    if (kinds == 0 || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
+    // the learn outcome decides for ARP and ND frames
+    if (n && (kinds & (EMURX_RSPK_ARP | EMURX_RSPK_ND)) && !d_lrn_outcome) return EMURX_EINVAL;
+    if (ev_cap == 0 || ev_cap > emurx_nsstat_max_events(h)) return EMURX_EINVAL;
+    if (((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ev & 7) || ((uintptr_t)d_info & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;  // the scratch is sized at emurx_open
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // no table is read, but the records are a classify's: behind the shipment like the calls they come from
+    if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
+    if (h->nss_dirty) {
+        if (!EMURX_HIP_OK(hipMemsetAsync(h->d_nss.p, 0, emurx_nss_scratch_bytes(h->cfg.max_frames, h->cfg.max_ns), st))) return EMURX_EDEVICE;
+        h->nss_dirty = false;
+    }
+    if (emurx_launch_nsstat(d_frames, d_desc, d_rec, n, kinds, d_rsp_outcome, d_lrn_outcome, d_ev, ev_cap, d_done, d_info,
+                            h->d_nss.p, h->cfg.max_frames, h->cfg.max_ns, st)) {
+        h->nss_dirty = true;
         return EMURX_EDEVICE;
     }
     return EMURX_OK;

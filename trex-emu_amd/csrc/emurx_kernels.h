@@ -196,6 +196,14 @@ int emurx_launch_learn(const uint8_t* frames, const emurx_desc* desc, const emur
                        const emurx_dev_tables& T, emurx_learn_ev* ev, uint32_t ev_cap, uint8_t* outcome, uint64_t* info,
                        void* scratch, uint32_t max_frames, hipStream_t st);
 
+// The per-Namespace counter fold (emurx_nsstat.hip): see emurx_nsstat_dev.  scratch:
+// emurx_nss_scratch_bytes(max_frames, max_ns) bytes, all zero before the first call; every call
+// leaves the accumulator rows and their flags zero.  n <= max_frames.  Three launches.
+size_t emurx_nss_scratch_bytes(uint32_t max_frames, uint32_t max_ns);
+int emurx_launch_nsstat(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n, uint32_t kinds,
+                        const uint8_t* rsp_outcome, const uint8_t* lrn_outcome, emurx_nsstat_ev* ev, uint32_t ev_cap,
+                        uint8_t* done, uint64_t* info, void* scratch, uint32_t max_frames, uint32_t max_ns, hipStream_t st);
+
 // Tx ZMQ framing (emurx_txzmq.hip): see emurx_tx_zmq_dev.  scratch: emurx_txz_scratch_bytes(n).
 size_t emurx_txz_scratch_bytes(uint32_t n);
 // variant: the write kernel's image (EMURX_TXZ_*, emurx_tx_zmq_dev's feedback choice); feedback:

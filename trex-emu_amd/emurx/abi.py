@@ -126,6 +126,26 @@ LRN_INFO_WORDS = 8
 LEARN_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("count", "<u4"), ("first", "<u4"), ("last", "<u4"), ("ip", "u1", 16),
                            ("mac", "u1", 6), ("kind", "u1"), ("pad", "u1")])
 assert LEARN_EV_DTYPE.itemsize == 40
+# enum emurx_nsc: the words of emurx_nsstat_ev.cnt (emurx_nsstat_dev); 6 and 10 stand for two Go
+# counters each, pktRxIcmpQuery and pktTxIcmpResponse
+(NSC_ARP_QUERY, NSC_ARP_QUERY_NOT_FOR_US, NSC_ARP_REPLY, NSC_ARP_ERR_NO_BROADCAST, NSC_ARP_ERR_WRONG_OP, NSC_ARP_TX_REPLY,
+ NSC_ICMP_ECHO, NSC_ICMP_NO_CLIENT, NSC_ICMP_ERR_MCAST, NSC_ICMP_ERR_UNHANDLED, NSC_V6_ECHO, NSC_V6_NO_CLIENT,
+ NSC_V6_ERR_MCAST, NSC_V6_ERR_UNHANDLED, NSC_ND_RX_NS, NSC_ND_TX_ADV_UNICAST, NSC_ND_TX_DAD_ERROR, NSC_ND_RX_NA,
+ NSC_ND_RX_NA_LEARN) = range(19)
+NSC_WORDS = 22
+NSS_INFO_WORDS = 8
+# the Go counters of each word: (plugin stats, names)
+NSC_GO = [("arp", ("pktRxArpQuery",)), ("arp", ("pktRxArpQueryNotForUs",)), ("arp", ("pktRxArpReply",)),
+          ("arp", ("pktRxErrNoBroadcast",)), ("arp", ("pktRxErrWrongOp",)), ("arp", ("pktTxReply",)),
+          ("icmp", ("pktRxIcmpQuery", "pktTxIcmpResponse")), ("icmp", ("pktRxNoClientUnhandled",)),
+          ("icmp", ("pktRxErrMulticastB",)), ("icmp", ("pktRxErrUnhandled",)),
+          ("ipv6", ("pktRxIcmpQuery", "pktTxIcmpResponse")), ("ipv6", ("pktRxNoClientUnhandled",)),
+          ("ipv6", ("pktRxErrMulticastB",)), ("ipv6", ("pktRxErrUnhandled",)),
+          ("nd", ("pktRxNeighborSolicitation",)), ("nd", ("pktTxNeighborAdvUnicast",)), ("nd", ("pktTxNeighborDADError",)),
+          ("nd", ("pktRxNeighborAdvertisement",)), ("nd", ("pktRxNeighborAdvLearn",))]
+# emurx_nsstat_ev: one event per Namespace with a frame whose handler is not needed
+NSSTAT_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("frames", "<u4"), ("cnt", "<u4", NSC_WORDS)])
+assert NSSTAT_EV_DTYPE.itemsize == 96
 FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xFFFFFFF0, 0xFFFFFFF1,
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
@@ -243,6 +263,8 @@ SIGNATURES = [
     ("emurx_learn_max_events", C.c_uint32, [_P]),
     ("emurx_learn_key_hash", C.c_uint32, [_P]),
     ("emurx_learn_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_nsstat_max_events", C.c_uint32, [_P]),
+    ("emurx_nsstat_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -300,7 +322,7 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
-           "emurx_respond.hip", "emurx_learn.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()

@@ -297,6 +297,24 @@ class RxPath:
         return abi.check(self.lib.emurx_learn_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds, _addr(ev),
                                                   ev_cap, _addr(outcome), _addr(info), _stream(stream)), "learn_dev")
 
+    def nsstat_max_events(self) -> int:
+        """The largest ev_cap nsstat_dev takes: min(max_frames, max_ns)."""
+        return int(self.lib.emurx_nsstat_max_events(self.h))
+
+    def nsstat_dev(self, frames, desc, rec, n: int, rsp_outcome, lrn_outcome, ev, ev_cap: int, done, info,
+                   kinds: int = abi.RSPK_ALL, stream=None):
+        """The ARP / ICMP / ICMPv6 / ND handlers' per-Namespace counters of a classified batch, folded
+        on the device (include/emu_rx.h emurx_nsstat_dev): rsp_outcome / lrn_outcome u8 [n] are the
+        outcome arrays of respond_dev(kinds=...) and learn_dev on the same batch (lrn_outcome may be
+        None without RSPK_ARP and RSPK_ND); ev abi.NSSTAT_EV_DTYPE [ev_cap], written in ascending
+        ns_id; done u8 [n] (0 the Go handler runs, 1 skip it, 2 skip it and count errParser; or
+        None); info u64[abi.NSS_INFO_WORDS] {events written, distinct Namespaces, overflow, frames
+        done 1, done 2, candidates left at 0, 0, 0}.  On overflow (distinct > ev_cap) no event is
+        written."""
+        return abi.check(self.lib.emurx_nsstat_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds,
+                                                   _addr(rsp_outcome), _addr(lrn_outcome), _addr(ev), ev_cap, _addr(done),
+                                                   _addr(info), _stream(stream)), "nsstat_dev")
+
     # ---- Namespace-partitioned exchange ---------------------------------------------------
     def classify_route_dev(self, frames, desc, n: int, rec, qlist, qcap: int, tile_cnt, hist, n_parts: int,
                            my_rank: int, cap: int, send, send_count, stream=None, flow=None):
