@@ -921,6 +921,13 @@ uint32_t emurx_last_stage(const emurx_t* h);
 #define EMURX_UNI_LOOKUP 2u
 #define EMURX_UNI_SAMPLED 4u
 int emurx_last_uniform(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]);
+/* One more fact about the same sampled waves, in the same layout: words[...] is
+   EMURX_UNI_SAMPLED, or-ed with EMURX_TRIM_RANGE when the wave read its byte range off its end
+   lanes (no empty slot, offsets and ends that never fall from one lane to the next) instead of
+   reducing over the lanes.  Results never depend on it.  Waits for the device.  A tuning
+   observable, no ABI replacement. */
+#define EMURX_TRIM_RANGE 1u
+int emurx_last_trim(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]);
 /* LDS image (bytes per wave) of the most recent tx framing write (emurx_tx_zmq_dev): 6144,
    4608 or 0 (every tile on the rows-over-lanes path); -1 before the first.  Chosen per call from
    the tile sizes an earlier call's chain kernel saw; EMURX_TXZ=wide|narrow|long at emurx_open

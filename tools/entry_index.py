@@ -58,7 +58,7 @@ GROUPS = [
      "the counters of `HandleRxArpPacket` `arp/arp.go:904-946`, `HandleRxIcmpPacket` `icmp/icmp.go:396-462`, "
      "`HandleRxIpv6Packet` `ipv6/ipv6.go:465-539`, `HandleRxIpv6NdPacket` `ipv6/nd.go:1546-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
-                     "emurx_last_uniform", "emurx_last_txz"],
+                     "emurx_last_uniform", "emurx_last_trim", "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),
 ]
 

@@ -850,10 +850,10 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
         const uint32_t cap = emurx_ingest_small_capacity(cfg->device);
         h->small_tiles = std::min<uint32_t>(EMURX_SMALL_TILES, cap);
     }
-    if (h->stage_fb.alloc(256) || h->d_stage_fb.alloc(2 * emurx::kFbWords) ||
+    if (h->stage_fb.alloc(256) || h->d_stage_fb.alloc(3 * emurx::kFbWords) ||
         !EMURX_HIP_OK(hipEventCreateWithFlags(&h->stage_ev, hipEventDisableTiming)) ||
         !EMURX_HIP_OK(hipEventCreateWithFlags(&h->ship_ev, hipEventDisableTiming)) ||
-        !EMURX_HIP_OK(hipMemset(h->d_stage_fb.p, 0, 2 * emurx::kFbWords * sizeof(uint32_t)))) {
+        !EMURX_HIP_OK(hipMemset(h->d_stage_fb.p, 0, 3 * emurx::kFbWords * sizeof(uint32_t)))) {
         emurx_close(h);
         return EMURX_ENOMEM;
     }
@@ -1335,6 +1335,16 @@ int emurx_last_uniform(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]) {
     // the words of the most recent launch alone (k_rx tags them with its generation)
     for (uint32_t i = 0; i < EMURX_UNI_WORDS; ++i)
         words[i] = h->stage_gen && (words[i] >> 2) == h->stage_gen ? EMURX_UNI_SAMPLED | (words[i] & 3u) : 0u;
+    return EMURX_OK;
+}
+int emurx_last_trim(emurx_t* h, uint32_t words[EMURX_UNI_WORDS]) {
+    if (!h || !words) return EMURX_EINVAL;
+    if (bind(h)) return EMURX_EDEVICE;
+    if (!EMURX_HIP_OK(hipDeviceSynchronize()) ||
+        !EMURX_HIP_OK(hipMemcpy(words, h->d_stage_fb.p + 2 * emurx::kFbWords, EMURX_UNI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost)))
+        return EMURX_EDEVICE;
+    for (uint32_t i = 0; i < EMURX_UNI_WORDS; ++i)  // as emurx_last_uniform: the most recent launch's words alone
+        words[i] = h->stage_gen && (words[i] >> 2) == h->stage_gen ? EMURX_UNI_SAMPLED | (words[i] & EMURX_TRIM_RANGE) : 0u;
     return EMURX_OK;
 }
 int32_t emurx_last_txz(const emurx_t* h) {

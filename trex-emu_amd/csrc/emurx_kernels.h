@@ -62,16 +62,17 @@ public:
 // bytes); waves whose frames span more than the slab take the window path
 namespace emurx {
 constexpr uint32_t kStageWide = 7168, kStageNarrow = 6144, kStageTight = 5120;
-// k_rx's feedback words: 64 sampled tiles x 4 waves of stage facts, then as many path words
+// k_rx's feedback words: 64 sampled tiles x 4 waves of stage facts, then as many path words,
+// then as many words for the range shortcut
 constexpr uint32_t kFbWords = 256;
 }
 
 // Enqueue one batch on `st`: a single k_rx launch, no host synchronisation (capturable in a
 // hipGraph).  ev[0..1] (optional) are recorded before and after it.  stage: the staging slab
 // per wave in bytes, 7168 (5 workgroups per CU), 6144 (6) or 5120 (7; emurx_parse.h kStage*;
-// every kind has all three).  fb (optional, 2 * kFbWords device words): the sampled tiles' stage
+// every kind has all three).  fb (optional, 3 * kFbWords device words): the sampled tiles' stage
 // feedback, tagged with gen (29 bits), then one word per sampled wave {gen << 2, the lookups took
-// the uniform-wave path << 1, the parse took it}.  uniform: staged waves whose frames share one
+// the uniform-wave path << 1, the parse took it}, then {gen << 2, range from the end lanes}.  uniform: staged waves whose frames share one
 // plain IPv4 udp / tcp shape take the uniform-wave path (emurx_parse.h); results never depend on
 // it.  Returns 0 or -1.
 // rt (optional, classify only): the route count pass fused into k_rx: per-(tile, owner) counts

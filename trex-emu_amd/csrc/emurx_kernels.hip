@@ -89,15 +89,28 @@ __device__ __forceinline__ uint2 load_desc(const emurx_desc* __restrict__ desc, 
 struct Stage {
     uint32_t start, nvec;
     bool staged;
+    bool dense;  // the range was read off the end lanes (no reduction)
 };
 template <uint32_t kStage>
 __device__ __forceinline__ Stage stage_issue(const uint8_t* __restrict__ frames, uint2 dd, uint32_t lane, uint4* wslab) {
     constexpr uint32_t kWinVec = kStage / 16 / kWave;  // window path: 16-byte vectors per lane
     const bool valid = (dd.y >> 24) != EMURX_DESC_HOLE;  // an empty slot is no frame at all
-    const uint32_t off = dd.x, len = dd.y & 0xffff;
-    const uint32_t lo = wave_min_u32(valid ? off : 0xffffffffu);
-    const uint32_t hi = wave_max_u32(valid ? off + len : 0u);
+    const uint32_t off = dd.x, len = dd.y & 0xffff, end = off + len;
+    // The range of a dense wave from its end lanes: no lane empty and neither the offsets nor
+    // the ends fall from one lane to the next (one neighbour move of each, one ballot), so the
+    // least offset is lane 0's and the greatest end lane 63's.  A hole, a permuted pair, a
+    // descriptor that steps back or a frame that ends before its predecessor does: the reductions
+    uint32_t lo, hi;
     Stage sg;
+    const uint32_t poff = wave_prev(off), pend = wave_prev(end);  // by every lane: no short circuit
+    sg.dense = __ballot(!valid | (off < poff) | (end < pend)) == 0;
+    if (sg.dense) {
+        lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+        hi = (uint32_t)__builtin_amdgcn_readlane((int)end, kWave - 1);
+    } else {
+        lo = wave_min_u32(valid ? off : 0xffffffffu);
+        hi = wave_max_u32(valid ? end : 0u);
+    }
     sg.start = lo & ~15u;
     sg.nvec = hi > lo ? (hi - sg.start + 15) >> 4 : 0;
     sg.staged = sg.nvec > 0 && sg.nvec <= kStage / 16;
@@ -213,6 +226,8 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
         const uint32_t bytes = sg.nvec * 16;
         const uint32_t mid = bytes > kStageNarrow && bytes <= kStageWide;
         a.fb[((tile >> 6) & 63) * kWaves + wv] = (a.gen << 3) | ((bytes > kStageTight) << 2) | ((sg.nvec > 0) << 1) | mid;
+        // a third word per wave: its range came from the end lanes (emurx_last_trim)
+        a.fb[2 * kFbWords + ((tile >> 6) & 63) * kWaves + wv] = (a.gen << 2) | (sg.dense ? 1u : 0u);
     }
 
     Rec r;
@@ -239,8 +254,12 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
         bool done = false;
         if constexpr (kParkRec) {
             typedef std::decay_t<decltype(s)> S;
-            volatile uint32_t* pa = &L.csum[wv][lane];
-            volatile uint32_t* pb = &L.park[wv][lane];
+            // pointers in the LDS address space (as glds16 casts its destination): a generic
+            // volatile pointer compiles to system-scope flat stores and loads, each with a wait
+            // of its own; these are ds_write_b32 / ds_read_b32
+            typedef volatile __attribute__((address_space(3))) uint32_t* LdsWord;
+            const LdsWord pa = (LdsWord)&L.csum[wv][lane];
+            const LdsWord pb = (LdsWord)&L.park[wv][lane];
             *pa = r.l4 | (r.l7 << 16);
             static_assert(EMURX_FLAG_RTALERT < 8 && EMURX_ST_PANIC_MBUF < 32, "flags and status share the parked byte");
             *pb = r.l7len | (r.nh << 16) | (r.flags << 24) | (r.status << 27);

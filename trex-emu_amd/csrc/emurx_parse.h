@@ -1541,10 +1541,27 @@ __device__ __forceinline__ void parse_uniform(const LdsSrc& s, uint32_t vport, u
     r.flags = 0;
     r.dlen = 0;
     r.flow = EMURX_FLOW_NONE;
-    const bool hok = csum_ok(s.template sum_fixed<20>(L3), s.at(L3), 0);
-    const uint32_t pcs = be_domain(s.template sum_fixed<8>(L3 + 12), s.at(L3 + 12)) + u.nh + l4len;  // src, dst, 0|proto, len
+    // The two verdicts of csum_ok without its byte swaps.  be_domain's swap is multiplication
+    // by 256 modulo 0xffff, which is invertible (256 * 256 == 1), and fold16 of a sum is 0 only
+    // for the sum 0: so `be_domain(T) + pcs` is 0 modulo 0xffff exactly where the unswapped sum
+    // is, once pcs's own terms are brought into T's domain.
+    //   header: pcs = 0, so the verdict is fold16(T20) == 0xffff (a zero sum, which csum_ok
+    //     refuses, folds to 0).  T20 as the sum over bytes [L3, L3 + 12) plus the sum ta over
+    //     the addresses [L3 + 12, L3 + 20): the same dwords under complementary masks, the same
+    //     integer, and ta is read once for both verdicts.
+    //   L4: pcs = be_domain(ta) + nh + l4len with L3 + 12 and L4 = L3 + 20 of one parity, so ta
+    //     adds to the span's sum as it is and c = nh + l4len (at most 17 + 65515: 16 bits) is
+    //     swapped where the span starts at an even address.  c >= 14 keeps the sum from being
+    //     zero, so csum_ok's `!(T == 0 && pcs == 0)` cannot fire here and the verdict is again
+    //     a fold to 0xffff.
+    //   The sums are added before the one fold: a span's sum is below 2^31 for any 16-bit length
+    //   (at most 16,385 dwords of two 16-bit halves each), ta and c' add less than 2^19.
+    const uint32_t ta = s.template sum_fixed<8>(L3 + 12);
+    const bool hok = fold16(s.template sum_fixed<12>(L3) + ta) == 0xffffu;
+    const uint32_t c = u.nh + l4len;
+    const uint32_t pd = ta + ((s.at(L4) & 1u) ? c : (__builtin_bswap32(c) >> 16));  // one value held across the span's sum
     // summed for every lane (a lane Go would not sum ignores the verdict)
-    const bool cs = csum_ok(span_sum_wave(s, L4, l4len), s.at(L4), pcs);
+    const bool cs = fold16(span_sum_wave(s, L4, l4len) + pd) == 0xffffu;
     uint32_t st, cb, l7, l7len;
     if (u.nh == 17) {  // scalar
         const bool ucs = (s.u8(L4 + 6) | s.u8(L4 + 7)) != 0;  // UDP checksum present

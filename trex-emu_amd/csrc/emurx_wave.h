@@ -73,6 +73,11 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return wave_reduce(v, [](uint32_t x, uint32_t y) { return x + y; });
 }
+// lane l - 1's value (0 in lane 0): one DPP move across the whole wave (wave_shr:1); called
+// with every lane active
+__device__ __forceinline__ uint32_t wave_prev(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
+}
 __device__ __forceinline__ uint32_t dpp_row_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2

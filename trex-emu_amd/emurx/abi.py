@@ -233,6 +233,7 @@ SIGNATURES = [
     ("emurx_kernel_times", C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("emurx_last_stage", C.c_uint32, [_P]),
     ("emurx_last_uniform", C.c_int, [_P, _P]),
+    ("emurx_last_trim", C.c_int, [_P, _P]),
     ("emurx_last_txz", C.c_int32, [_P]),
     ("emurx_copy_ceiling_dev", C.c_int, [_P, _P, C.c_size_t, _P]),
     ("emurx_ns_owner", C.c_uint32, [_U8P, C.c_uint32]),
@@ -284,8 +285,9 @@ SIGNATURES = [
 
 # measurement observables that an older library given through EMURX_LIB (A/B runs of one
 # bench.py against two builds) may lack; calling one it lacks is an AttributeError
-OPTIONAL = {"emurx_last_uniform"}
+OPTIONAL = {"emurx_last_uniform", "emurx_last_trim"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
+TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 
 _lib = None
 

@@ -209,6 +209,13 @@ class RxPath:
         abi.check(self.lib.emurx_last_uniform(self.h, _p(w)), "last_uniform")
         return w
 
+    def last_trim(self) -> np.ndarray:
+        """The same sampled waves as last_uniform, same layout: abi.UNI_SAMPLED | abi.TRIM_RANGE
+        (the wave took its byte range from its end lanes instead of reducing)."""
+        w = np.zeros(abi.UNI_WORDS, np.uint32)
+        abi.check(self.lib.emurx_last_trim(self.h, _p(w)), "last_trim")
+        return w
+
     def last_txz(self) -> int:
         """LDS image bytes per wave of the last tx framing write (6144, 4608, 0; -1 before)."""
         return int(self.lib.emurx_last_txz(self.h))
