@@ -13,7 +13,7 @@ import kat_frames as K
 from emurx import abi
 from emurx import frames as F
 from emurx import synth
-from gpu_util import frames_tables, load_frame_tables, owner_keys, rec_diff, run_dev
+from gpu_util import frames_tables, load_frame_tables, owner_keys, rec_diff, run_dev, to_dev
 
 pytestmark = pytest.mark.gpu
 ALL = (1 << 12) - 1
@@ -606,6 +606,74 @@ def test_holes_records_and_route(rxmod):
         sreg = send.cpu().numpy().view(abi.ROUTE_REC_DTYPE).reshape(4, cap)
         for k in range(4):
             assert sreg[k, : c[k]].tobytes() == wroute[k].tobytes(), (fused, k)
+
+
+def test_one_wave_holds_every_queue_and_owner(rxmod):
+    """One wave whose 64 lanes hold every id the rank loops meet at once: 62 frames of eight
+    queues (seven callbacks and the drop queue) in scrambled lane order and two empty descriptor
+    slots, on Namespaces of all eight owners plus frames that are dropped or find no Namespace
+    (no owner).  Records, queue lists and offsets, and the 8-way send regions and counts,
+    standalone and fused, equal the oracle's bit for bit; no byte past a region's count is
+    written."""
+    import torch
+    import route_ref
+    from emurx import exchange as X
+    n, n_parts, my_rank, n_vports, known = 64, 8, 3, 40, 37
+    kinds = [E.udp4(1000, 2000), E.tcp4(), E.icmp6(128), E.udp4(67, 68), E.eth(F.ETH_EAPOL, b"\x01\x00\x00\x05"),
+             E.eth(F.ETH_ARP, F.arp(1, E.S, "1.1.1.1", "00:00:00:00:00:00", "1.1.1.2")),
+             E.eth(F.ETH_PPPOE_DISC, F.pppoe_padi()),
+             E.v4(17, F.udp(1, 2, b"x", csum=0), csum=0x1234), bytes(13)]  # the last two are dropped
+    rng = np.random.default_rng(64)
+    holes = np.array([17, 40])
+    keep = np.setdiff1d(np.arange(n), holes)
+    pick = rng.permutation(np.arange(n) % len(kinds))  # every kind 7 or 8 times, lanes scrambled
+    vports = rng.integers(0, n_vports, n)              # vports >= known have no Namespace
+    buf, desc = F.pack_frames([kinds[k] for k in pick], [int(v) for v in vports])
+    desc["pad"][holes] = abi.DESC_HOLE
+    rx, o = new_pair(rxmod)
+    load_frame_tables([rx, o], {F.tunnel_key(v, 0, 0): v for v in range(known)}, {})
+    # the oracle alone: what the batch holds
+    orec, oq, oqoff, _ = o.rx_batch(buf, desc[keep])
+    want = np.zeros(n, abi.REC_DTYPE)
+    want[keep] = orec
+    want[holes] = _hole_rec()
+    wq = keep[oq].astype(np.uint32)
+    own = route_ref.owners(want, n_parts)
+    assert int((np.diff(oqoff.astype(np.int64)) > 0).sum()) >= 6
+    assert sorted(set(own[own != 0xFF])) == list(range(n_parts))
+    assert (orec["status"] != 0).any() and ((orec["status"] == 0) & (orec["ns_id"] == abi.ID_NONE)).any()
+    wroute = route_ref.route(want, n_parts, my_rank)
+    # classify alone
+    rec, qlist, qoff, hist = run_dev(rx, buf, desc)
+    assert rec.tobytes() == want.tobytes(), rec_diff(rec, want)
+    assert np.array_equal(qoff, oqoff) and np.array_equal(qlist, wq)
+    assert int(hist[0::2].sum()) == len(keep)
+    # the route, standalone over the records and fused into the classify launch
+    from emurx.rx import pack_queues
+    tb, td = to_dev(buf), to_dev(desc)
+    drec = torch.from_numpy(want.view(np.uint8).copy()).cuda()
+    cap = X.capacity(n, n_parts)
+    for fused in (False, True):
+        send = torch.full((n_parts * cap * X.REC_BYTES,), 0xEE, dtype=torch.uint8, device="cuda")
+        cnt = torch.full((n_parts,), -1, dtype=torch.int32, device="cuda")
+        if fused:
+            d = _dev_out(n)
+            rx.classify_route_dev(tb, td, n, d["rec"], d["qlist"], d["qcap"], d["tile_cnt"], d["hist"], n_parts,
+                                  my_rank, cap, send, cnt)
+        else:
+            rx.route_dev(drec, n, n_parts, my_rank, cap, send, cnt)
+        torch.cuda.synchronize()
+        if fused:
+            frec = d["rec"].cpu().numpy()[: n * 32].view(abi.REC_DTYPE)
+            assert frec.tobytes() == want.tobytes(), rec_diff(frec, want)
+            fq, fqoff = pack_queues(d["qlist"].cpu().numpy(), d["qcap"], d["tile_cnt"].cpu().numpy(), n)
+            assert np.array_equal(fqoff, oqoff) and np.array_equal(fq, wq)
+        c = cnt.cpu().numpy()
+        assert list(c) == [len(x) for x in wroute], fused
+        sreg = send.cpu().numpy().reshape(n_parts, cap * X.REC_BYTES)
+        for k in range(n_parts):
+            assert sreg[k, : c[k] * X.REC_BYTES].tobytes() == wroute[k].tobytes(), (fused, k)
+            assert (sreg[k, c[k] * X.REC_BYTES:] == 0xEE).all(), (fused, k)
 
 
 def test_route_dev_overflow(rxmod):

@@ -486,16 +486,7 @@ __global__ __launch_bounds__(kBlock) void k_ingest_small(const SmallArgs a) {
         atomicAdd(&s_hp[bin], 1u);
         atomicAdd(&s_hb[bin], len);
     }
-    uint32_t rank = 0;
-    uint64_t left = __ballot(q != 0xffu);
-    while (left) {
-        const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1;
-        const uint32_t qq = (uint32_t)__builtin_amdgcn_readlane((int)q, (int)lead);
-        const uint64_t m = __ballot(q == qq);
-        if (q == qq) rank = mbcnt(m);
-        if (lane == lead) s_wcnt[wv][qq] = (uint32_t)__popcll(m);
-        left &= ~m;
-    }
+    const uint32_t rank = wave_rank_by_id(q, q != 0xffu, lane, s_wcnt[wv]);
     __syncthreads();
     if (a.nt == 1) {
         // one tile: queues, qoff and the histogram straight from LDS into the host buffers, no

@@ -49,11 +49,6 @@ __device__ unsigned long long* g_stamp;
 
 // k_rx's arguments as one struct (a single kernarg block; 91 SGPRs and 76 VGPRs against 106
 // and 79 for the same arguments passed one by one)
-// EMURX_TOL_PREFETCH (default 1): k_rx<2> issues the tile's owner-offset loads before the
-// staging wait (0, A/B builds: wave 0 loads them inside the tile body, one more round trip)
-#ifndef EMURX_TOL_PREFETCH
-#define EMURX_TOL_PREFETCH 1
-#endif
 struct RxArgs {
     const uint8_t* frames;
     const emurx_desc* desc;
@@ -76,11 +71,6 @@ __device__ __forceinline__ uint2 load_desc(const emurx_desc* __restrict__ desc, 
     return i < n ? *reinterpret_cast<const uint2*>(desc + i) : make_uint2(0, EMURX_DESC_HOLE << 24);
 }
 
-// EMURX_WIN_NT (build variant, A/B): non-temporal window loads (with EMURX_WSKIP the
-// cooperative pass reads no window byte again)
-#ifndef EMURX_WIN_NT
-#define EMURX_WIN_NT 0
-#endif
 // The wave's staging of its 64 frames into its slab (wslab: the wave's kStage bytes):
 // the byte range [lo, hi) of the wave's frames copied HBM -> LDS by LDS-DMA
 // (global_load_lds_dwordx4, no VGPR round trip) when it fits the slab, else a window of each
@@ -129,7 +119,7 @@ __device__ __forceinline__ Stage stage_issue(const uint8_t* __restrict__ frames,
         const uint32_t nv = valid ? (uint32_t)(((fa & 15) + len + 15) >> 4) : 0;  // vectors of the frame
 #pragma unroll
         for (uint32_t k = 0; k < kWinVec; ++k)
-            if (k < nv) glds16<EMURX_WIN_NT != 0>(src + k, wslab + k * kWave);  // the span past it is read again
+            if (k < nv) glds16<false>(src + k, wslab + k * kWave);  // the span past it is read again
     }
     return sg;
 }
@@ -138,24 +128,6 @@ __device__ __forceinline__ Stage stage_issue(const uint8_t* __restrict__ frames,
 __device__ __forceinline__ void stage_wait() {
     wait_vm0();
     wave_lds_sync();
-}
-
-// EMURX_MATCHRANK (build variant, A/B): rank the lanes of a queue / an owner by one ballot
-// per bit of its id (the lanes holding the same id, as match_any) instead of one loop
-// iteration of scalar bookkeeping per distinct id present in the wave
-#ifndef EMURX_MATCHRANK
-#define EMURX_MATCHRANK 0
-#endif
-template <int kBits>
-__device__ __forceinline__ uint64_t match_lanes(uint32_t v, uint64_t act) {
-    uint64_t m = act;
-#pragma unroll
-    for (int b = 0; b < kBits; ++b) {
-        const bool bit = (v >> b) & 1u;
-        const uint64_t x = __ballot(bit);
-        m &= bit ? x : ~x;
-    }
-    return m;
 }
 
 // The workgroup's small LDS arrays of one tile.  kPark (the tight slab's classify build): a
@@ -214,8 +186,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     // kind 2: the tile's offset in every owner region, from the loads issued before the staging
     // wait (k_rx): in flight beside the tile's LDS-DMA instead of one more round trip here
     if (kKind == 2 && wv == 0) {
-        const TileOffLoads t = EMURX_TOL_PREFETCH ? tol : tile_offsets_issue(rt.cnt, rt.goff, rt.parts, tile, lane);
-        tile_offsets_sum(t, rt.parts, lane, L.toff);
+        tile_offsets_sum(tol, rt.parts, lane, L.toff);
     }
     const bool valid = (dd.y >> 24) != EMURX_DESC_HOLE;
     const uint32_t off = dd.x, len = dd.y & 0xffff, vport = (dd.y >> 16) & 0xff;
@@ -352,7 +323,8 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     // units: per (wave, owner) one atomic on the owner's cursor of this tile's shard (a line
     // each) takes the units of the wave's tails (tails of 1 and 3 units ranked by two ballots).
     // Issued here, consumed after the tile barrier (store_tails): the histogram, the queue ranks
-    // and the barrier hide the atomic's round trip
+    // and the barrier hide the atomic's round trip.  The loop is wave_rank_by_id written out: it
+    // ranks the tails and takes the tail cursor in the same iteration, on the same owner ballot
     uint32_t rd = 0xffu, rrank = 0, tofs = 0, tlead = 0, tb = 0;
     const uint32_t shard = tile & (EMURX_TAIL_SHARDS - 1);
     if constexpr (kKind == 2) {
@@ -426,29 +398,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     }
     const uint32_t q = valid ? (r.status == EMURX_ST_OK ? r.proto : EMURX_Q_DROP) : 0xffu;
     // rank inside (wave, queue): one ballot per distinct queue present in the wave
-    uint32_t rank = 0;
-#if EMURX_MATCHRANK
-    if (EMURX_MATCHRANK == 2 && __ballot(valid && q != (uint32_t)__builtin_amdgcn_readfirstlane((int)q)) == 0) {
-        // hybrid: one queue in the wave (or none)
-        const uint64_t vm = __ballot(valid);
-        rank = mbcnt(vm);
-        if (valid && rank == 0) L.wcnt[wv][q] = (uint32_t)__popcll(vm);
-    } else {
-        const uint64_t m = match_lanes<4>(q, __ballot(valid));
-        rank = mbcnt(m);
-        if (valid && rank == 0) L.wcnt[wv][q] = (uint32_t)__popcll(m);
-    }
-#else
-    uint64_t left = __ballot(valid);
-    while (left) {
-        const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1;
-        const uint32_t qq = (uint32_t)__builtin_amdgcn_readlane((int)q, (int)lead);
-        const uint64_t m = __ballot(q == qq);
-        if (q == qq) rank = mbcnt(m);
-        if (lane == lead) L.wcnt[wv][qq] = (uint32_t)__popcll(m);
-        left &= ~m;
-    }
-#endif
+    const uint32_t rank = wave_rank_by_id(q, valid, lane, L.wcnt[wv]);
     STAMP(5);
     STAMP(6);
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -490,21 +440,7 @@ __device__ __forceinline__ void tile_body(const RxArgs& a, uint32_t tile, uint2 
     if (kKind == 1 && rt.cnt) {
         const bool routed = valid && r.ns != EMURX_ID_NONE;
         rd = !routed ? 0xffu : emurx_owner(emurx_tk_hash(r.vport, r.vlan0, r.vlan1), rt.parts);
-#if EMURX_MATCHRANK
-        const uint64_t m = match_lanes<3>(rd, __ballot(rd != 0xffu));
-        rrank = mbcnt(m);
-        if (rd != 0xffu && rrank == 0) L.rcnt[wv][rd] = (uint32_t)__popcll(m);
-#else
-        uint64_t rl = __ballot(rd != 0xffu);
-        while (rl) {
-            const uint32_t lead = (uint32_t)__ffsll((long long)rl) - 1;
-            const uint32_t dd2 = (uint32_t)__builtin_amdgcn_readlane((int)rd, (int)lead);
-            const uint64_t m = __ballot(rd == dd2);
-            if (rd == dd2) rrank = mbcnt(m);
-            if (lane == lead) L.rcnt[wv][dd2] = (uint32_t)__popcll(m);
-            rl &= ~m;
-        }
-#endif
+        rrank = wave_rank_by_id(rd, rd != 0xffu, lane, L.rcnt[wv]);
     }
     STAMP(7);
     __syncthreads();
@@ -587,7 +523,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStage =
 #endif
     const uint2 dd = load_desc(a.desc, a.n, tile * EMURX_QUEUE_TILE + threadIdx.x);
     TileOffLoads tol{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), 0u};
-    if (EMURX_TOL_PREFETCH && kKind == 2 && wv == 0) tol = tile_offsets_issue(a.rt.cnt, a.rt.goff, a.rt.parts, tile, lane_id());
+    if (kKind == 2 && wv == 0) tol = tile_offsets_issue(a.rt.cnt, a.rt.goff, a.rt.parts, tile, lane_id());
 #if EMURX_STAMP
     wait_vm0();
     pre[1] = __builtin_amdgcn_s_memtime();
@@ -627,9 +563,6 @@ int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n
                        bool uniform, const emurx_route_args* rt) {
     using namespace emurx;
     hipError_t e = hipSuccess;
-#ifndef EMURX_RX_LDS_PAD  // measurement builds only: unused LDS per workgroup, to cap k_rx's occupancy
-#define EMURX_RX_LDS_PAD 0
-#endif
     if (ev && !EMURX_HIP_OK(hipEventRecord(ev[0], st))) return -1;
     if (n) {
         const uint32_t ntiles = (n + EMURX_QUEUE_TILE - 1) / EMURX_QUEUE_TILE;
@@ -644,7 +577,7 @@ int emurx_launch_batch(const uint8_t* frames, const emurx_desc* desc, uint32_t n
         auto k = kind == 1 ? (tight ? k_rx<1, kStageTight> : narrow ? k_rx<1, kStageNarrow> : k_rx<1, kStageWide>)
                : kind == 2 ? (tight ? k_rx<2, kStageTight> : narrow ? k_rx<2, kStageNarrow> : k_rx<2, kStageWide>)
                            : (tight ? k_rx<0, kStageTight> : narrow ? k_rx<0, kStageNarrow> : k_rx<0, kStageWide>);
-        e = emurx_launch(k, dim3(ntiles), dim3(kBlock), EMURX_RX_LDS_PAD, st, args);
+        e = emurx_launch(k, dim3(ntiles), dim3(kBlock), 0, st, args);
     }
     if (!EMURX_HIP_OK(e)) return -1;
     return ev && !EMURX_HIP_OK(hipEventRecord(ev[1], st)) ? -1 : 0;

@@ -97,29 +97,12 @@ __device__ __forceinline__ bool csum_ok(uint32_t T, uint32_t a_start, uint32_t p
 }
 // sum over the bytes [a, a + n) of a dword sequence w[k] (byte a at dword a >> 2):
 // head / body / tail masks, body unmasked
-#ifndef EMURX_SHORTSUM
-#define EMURX_SHORTSUM 0
-#endif
 template <class A>
 __device__ __forceinline__ uint32_t dword_sum(const A& w, uint32_t a, uint32_t n) {
     if (n == 0) return 0;
     const uint32_t e = a + n, k0 = a >> 2, k1 = (e - 1) >> 2;
     const uint32_t hm = 0xffffffffu << (8 * (a & 3));
     const uint32_t tm = 0xffffffffu >> (8 * ((0u - e) & 3));
-#if EMURX_SHORTSUM
-    // a span of at most 64 bytes (17 dwords): every dword read at once, the ones past the span
-    // masked to nothing (one LDS round trip instead of one per four dwords); wave-uniform test
-    if (__builtin_amdgcn_ballot_w64(k1 - k0 > 16) == 0) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (uint32_t j = 0; j <= 16; ++j) {
-            const uint32_t k = k0 + j;
-            const uint32_t m = k > k1 ? 0u : (j == 0 ? hm : 0xffffffffu) & (k == k1 ? tm : 0xffffffffu);
-            acc = sad16(w[k] & m, acc);  // read unconditionally: a dword past the span is in LDS
-        }
-        return acc;
-    }
-#endif
     const uint32_t w0 = w[k0] & hm;
     if (k0 == k1) return sad16(w0 & tm, 0);
     uint32_t acc = sad16(w0, 0), k = k0 + 1;
@@ -285,19 +268,16 @@ template <class S>
 __device__ __forceinline__ bool csum_l4(const S& s, Rec& r, uint32_t at, uint32_t n, uint32_t pcs, uint32_t fail_st) {
     return csum(s, at, n, pcs);
 }
-// EMURX_WSKIP (default since round 4; =0 the round-3 re-read): the span's bytes inside the window are summed from LDS
-// here and folded into the deferred pseudo sum (the byte-pair sum is linear mod 0xffff, and
-// be_domain with the span's own start parity orients both parts alike), so the cooperative
-// pass reads only the bytes past the window: every span byte crosses HBM once
-#ifndef EMURX_WSKIP
-#define EMURX_WSKIP 1
-#endif
+// the span's bytes inside the window are summed from LDS here and folded into the deferred
+// pseudo sum (the byte-pair sum is linear mod 0xffff, and be_domain with the span's own start
+// parity orients both parts alike), so the cooperative pass reads only the bytes past the
+// window: every span byte crosses HBM once
 template <>
 __device__ __forceinline__ bool csum_l4<WinSrc>(const WinSrc& s, Rec& r, uint32_t at, uint32_t n, uint32_t pcs,
                                                 uint32_t fail_st) {
     if (at + n <= s.wlim || n == 0) return csum(s, at, n, pcs);
     uint32_t st = at, pw = pcs;
-    if (EMURX_WSKIP && at < s.wlim) {
+    if (at < s.wlim) {
         const uint32_t tw = dword_sum(WinDw{s.b32 + (s.wbase >> 2)}, s.head + at, s.wlim - at);
         pw = pcs + be_domain(tw, s.at(at));  // tw == 0 leaves pcs as it was (Go's all-zero case)
         st = s.wlim;
@@ -510,11 +490,6 @@ __device__ __forceinline__ void first(uint32_t& st, bool cond, uint32_t code) {
     st = (st == EMURX_ST_OK && cond) ? code : st;
 }
 
-// EMURX_DWFIELDS: header fields of the staged path extracted from aligned-dword words (v_alignbyte)
-// instead of byte reads (A/B)
-#ifndef EMURX_DWFIELDS
-#define EMURX_DWFIELDS 0
-#endif
 // Parser.parsePacketL4 parser.go:583-724, flat
 __device__ __forceinline__ void parse_l4_flat(const LdsSrc& s, uint32_t len, Rec& r, uint32_t nextHdr, uint32_t pcs,
                                               uint32_t l4len, bool v6, uint32_t cb_mask) {
@@ -523,16 +498,8 @@ __device__ __forceinline__ void parse_l4_flat(const LdsSrc& s, uint32_t len, Rec
     const bool p1 = nextHdr == 1, p2 = nextHdr == 2, p6 = nextHdr == 6, p17 = nextHdr == 17, p58 = nextHdr == 58;
     const uint32_t L4_8 = (L4 + 8) & 0xffff, L4_4 = (L4 + 4) & 0xffff, L4_12 = (L4 + 12) & 0xffff;
     const bool sok = span_ok(L4, l4len);
-#if EMURX_DWFIELDS
-    // the L4 header's fields from three aligned-dword words (bytes L4..L4+7, L4+12..L4+15)
-    // instead of eight byte reads; a staged frame's L4 + 12 never wraps the uint16
-    const uint32_t P0 = le32(s, L4), P4 = le32(s, L4 + 4), P12 = le32(s, L4 + 12);
-    const uint32_t tcplen = ((P12 & 0xff) >> 4) << 2;
-    const bool ucs = (P4 >> 16) != 0;  // UDP checksum present (bytes L4+6, L4+7)
-#else
     const uint32_t tcplen = (s.u8(L4_12) >> 4) << 2;
     const bool ucs = be16(s, L4 + 6) > 0;  // UDP checksum present
-#endif
     uint32_t st = EMURX_ST_OK;
     bool tcp_hdr = false;  // TCP got past its length checks (L7 / L7Len are set)
     if (p1) {
@@ -562,12 +529,7 @@ __device__ __forceinline__ void parse_l4_flat(const LdsSrc& s, uint32_t len, Rec
     // before it for UDP, L7 only on success for ICMP and UDP)
     r.l7len = tcp_hdr ? ((l4len - tcplen) & 0xffff) : (p17 && len >= L4_8) ? ((l4len - 8) & 0xffff) : 0u;
     r.l7 = tcp_hdr ? ((L4 + tcplen) & 0xffff) : ((p1 || p17) && st == EMURX_ST_OK) ? L4_8 : 0u;
-#if EMURX_DWFIELDS
-    const uint32_t src = ((P0 & 0xff) << 8) | ((P0 >> 8) & 0xff), dst = (((P0 >> 16) & 0xff) << 8) | (P0 >> 24),
-                   t6 = P0 & 0xff;
-#else
     const uint32_t src = be16(s, L4), dst = be16(s, L4 + 2), t6 = s.u8(L4);
-#endif
     uint32_t cb = p1 ? EMURX_CB_ICMP : p2 ? EMURX_CB_IGMP : p6 ? EMURX_CB_TCP : p58 ? EMURX_CB_ICMPV6 : EMURX_CB_UDP;
     if (p17) {
         cb = dst == 5353 ? EMURX_CB_MDNS
@@ -593,14 +555,7 @@ __device__ __forceinline__ void parse_flat(const LdsSrc& s, uint32_t len, uint32
     auto is_ppp = [](uint32_t x) { return x == 0x8863 || x == 0x8864; };
     uint32_t st = EMURX_ST_OK;
     first(st, len < 14, EMURX_ST_PACKET_TOO_SHORT);
-#if EMURX_DWFIELDS
-    // bytes 12..23 as three big-endian words from four aligned dwords (the EtherType / TPID
-    // words and the CTunnelKey VLAN words) instead of six byte reads and two word reads
-    const uint32_t W12 = be32(s, 12), W16 = be32(s, 16), W20 = be32(s, 20);
-    const uint32_t e0 = W12 >> 16, e1 = W16 >> 16, e2 = W20 >> 16;
-#else
     const uint32_t e0 = be16(s, 12), e1 = be16(s, 16), e2 = be16(s, 20);
-#endif
     const bool t0 = st == EMURX_ST_OK && is_tag(e0);
     first(st, t0 && len < 18, EMURX_ST_DOT1Q_TOO_SHORT);
     const bool g0 = t0 && st == EMURX_ST_OK;  // tag 0 parsed
@@ -612,13 +567,8 @@ __device__ __forceinline__ void parse_flat(const LdsSrc& s, uint32_t len, uint32
     const bool t2 = g1 && !ppp1 && is_tag(e2);
     first(st, t2 && len < 26, EMURX_ST_DOT1Q_TOO_SHORT);
     first(st, t2, EMURX_ST_TOO_MANY_DOT1Q);
-#if EMURX_DWFIELDS
-    r.vlan0 = g0 ? (W12 & 0xffff0fffu) : 0u;
-    r.vlan1 = g1 ? (W16 & 0xffff0fffu) : 0u;
-#else
     r.vlan0 = g0 ? (be32(s, 12) & 0xffff0fffu) : 0u;
     r.vlan1 = g1 ? (be32(s, 16) & 0xffff0fffu) : 0u;
-#endif
     if (st != EMURX_ST_OK) { fail(r, st); return; }
     if (ppp0 || ppp1) { invoke(r, EMURX_CB_PPP, cb_mask); return; }
     const uint32_t offset = 14 + (g0 ? 4u : 0u) + (g1 ? 4u : 0u);
@@ -628,15 +578,7 @@ __device__ __forceinline__ void parse_flat(const LdsSrc& s, uint32_t len, uint32
     bool v6 = false;
     if (et == 0x0800) {  // IPv4
         r.l3 = offset;
-#if EMURX_DWFIELDS
-        // version / IHL, total length, flags / fragment offset and protocol from the header's
-        // first three words (the dwords its checksum reads again) instead of six byte reads
-        const uint32_t H0 = le32(s, offset), H4 = le32(s, offset + 4), H8 = le32(s, offset + 8);
-        const uint32_t b0 = H0 & 0xff, totlen = (((H0 >> 16) & 0xff) << 8) | (H0 >> 24),
-                       frag = (((H4 >> 16) & 0xff) << 8) | (H4 >> 24);
-#else
         const uint32_t b0 = s.u8(offset), frag = be16(s, offset + 6), totlen = be16(s, offset + 2);
-#endif
         const uint32_t hdr = (b0 & 0xf) << 2;
         first(st, len < offset + 20, EMURX_ST_IPV4_TOO_SHORT);
         first(st, (b0 >> 4) != 4, EMURX_ST_IPV4_HDR_TOO_SHORT);
@@ -651,11 +593,7 @@ __device__ __forceinline__ void parse_flat(const LdsSrc& s, uint32_t len, uint32
         if (st != EMURX_ST_OK) { fail(r, st); return; }
         l4len = (totlen - hdr) & 0xffff;
         l4 = offset + hdr;
-#if EMURX_DWFIELDS
-        nh = (H8 >> 8) & 0xff;
-#else
         nh = s.u8(offset + 9);
-#endif
         pcs = be_domain(s.template sum_fixed<8>(offset + 12), s.at(offset + 12)) + nh + l4len;  // src, dst, 0|proto, len
     } else if (et == 0x86DD) {  // IPv6
         r.l3 = offset;
@@ -730,9 +668,6 @@ __device__ __forceinline__ uint32_t span_sum(const uint4& x, uint32_t nv, int h,
     if (k >= nv) return 0;
     return sad_vec_masked(x, k == 0 ? h : 0, k == nv - 1 ? t : 16, 0);
 }
-#ifndef EMURX_COOP_NT
-#define EMURX_COOP_NT 0
-#endif
 // The wave's spans [span, span + n) (lanes with mine set) summed by its four 16-lane rows in
 // the dword form of glb_sum (sad of 16-bit halves, bytes outside the span masked): returns this
 // lane's sum (0 when not mine).  wsum: kWave words of LDS owned by the wave.  Called converged.
@@ -772,16 +707,7 @@ __device__ __forceinline__ uint32_t coop_span_sum(const uint8_t* span, uint32_t 
 #pragma unroll
         for (uint32_t k = 0; k < kCoopVec; ++k) {
             const uint32_t v = c * kRound + k * 16 + l16;
-#if EMURX_COOP_NT  // build variant (A/B): the span bytes are read once, never again
-            if (v < nvj) {
-                const emurx_v4u y = __builtin_nontemporal_load((const __attribute__((address_space(1))) emurx_v4u*)(src + 16 * v));
-                x[k] = make_uint4(y.x, y.y, y.z, y.w);
-            } else {
-                x[k] = make_uint4(0, 0, 0, 0);
-            }
-#else
             x[k] = v < nvj ? gld16(src + 16 * v) : make_uint4(0, 0, 0, 0);
-#endif
         }
         uint32_t part = 0;
 #pragma unroll
@@ -1119,12 +1045,7 @@ __device__ __forceinline__ LKey make_key(const S& s, uint32_t len, const Rec& r)
     const uint32_t cb = r.proto;
     LKey k;
     k.dlo = le32(s, 0);
-#if EMURX_DWFIELDS
-    if constexpr (std::is_same<S, LdsSrc>::value) k.dhi = le32(s, 4) & 0xffffu;  // p[4:6] from a dword word
-    else k.dhi = s.u8(4) | (s.u8(5) << 8);
-#else
     k.dhi = s.u8(4) | (s.u8(5) << 8);  // p[0:6]
-#endif
     k.mc6 = 0;
     const bool bcast = k.dlo == 0xffffffffu && k.dhi == 0xffffu;
     k.key = kMac;
@@ -1183,9 +1104,6 @@ struct Probe {
     const uint32_t* ctab;
     Bucket ne;
 };
-#ifndef EMURX_UNIHASH
-#define EMURX_UNIHASH 0
-#endif
 __device__ __forceinline__ Probe probe_issue(const emurx_dev_tables& T, const Rec& r, const LKey& k) {
     Probe p;
     const uint32_t key = k.key;
@@ -1196,19 +1114,7 @@ __device__ __forceinline__ Probe probe_issue(const emurx_dev_tables& T, const Re
                 (((k.kw[3] >> 8) & 0xff) << 24);
         p.mhi = ((k.kw[3] >> 16) & 0xff) | ((k.kw[3] >> 24) << 8);
     }
-#if EMURX_UNIHASH
-    // a wave whose frames share one CTunnelKey (one port's untagged or one-VLAN traffic) or
-    // one MAC key hashes it once, on the scalar unit (build variant for A/B)
-    const uint32_t u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.vport),
-                   u1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.vlan0),
-                   u2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.vlan1);
-    const bool tku = __ballot(r.vport != u0 || r.vlan0 != u1 || r.vlan1 != u2) == 0;
-    uint32_t tk;
-    if (tku) tk = emurx_tk_hash(u0, u1, u2);  // wave-uniform branch: scalar arithmetic
-    else tk = emurx_tk_hash(r.vport, r.vlan0, r.vlan1);
-#else
     const uint32_t tk = emurx_tk_hash(r.vport, r.vlan0, r.vlan1);  // CTunnelKey words
-#endif
     p.nb = tk & T.ns_mask;
     p.ne = ld_bucket(T.ns_tab, p.nb);
     p.cbk = 0;
@@ -1219,15 +1125,7 @@ __device__ __forceinline__ Probe probe_issue(const emurx_dev_tables& T, const Re
     uintptr_t tm = (uintptr_t)T.mac_tab, t4 = (uintptr_t)T.ip4_tab, t6 = (uintptr_t)T.ip6_tab;
     asm volatile("" : "+s"(tm), "+s"(t4), "+s"(t6));
     if (key == kMac || key == kEui) {
-#if EMURX_UNIHASH
-        const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.mlo),
-                       m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.mhi);
-        const bool mu = tku && __ballot(p.mlo != m0 || p.mhi != m1) == 0;
-        if (mu) p.cbk = emurx_mac_hash((uint32_t)__builtin_amdgcn_readfirstlane((int)tk), m0, m1) & T.mac_mask;
-        else p.cbk = emurx_mac_hash(tk, p.mlo, p.mhi) & T.mac_mask;
-#else
         p.cbk = emurx_mac_hash(tk, p.mlo, p.mhi) & T.mac_mask;
-#endif
         p.ctab = reinterpret_cast<const uint32_t*>(tm);
     } else if (key == kIp4) {
         p.cbk = emurx_ip4_hash(tk, k.kw[0]) & T.ip4_mask;
@@ -1327,130 +1225,13 @@ __device__ __forceinline__ void resolve_done(const emurx_dev_tables& T, Rec& r, 
     resolve_done(T, r, k, p, ce, flow, [&]() { return make_uint3(k.dlo, k.dhi, k.mc6); });
 }
 
-// The same outcome as resolve_done with far fewer divergent branches (EMURX_FLATRES, build
-// variant for A/B): every table kind's answer from the first buckets by straight-line selects
-// (the client bucket read as MAC, IPv4 and IPv6 slots at once: the lane's key kind picks one),
-// probe chains past the first bucket behind one wave-uniform test (the sparse tables make them
-// rare), the rule's outcome by selects, and the rules that read memory again (GetFirstClient,
-// the EUI-64 RA-prefix check, the transport flow) behind wave-uniform "any lane" tests.  The
-// divergent switch over key kinds in resolve_done costs its wave exec-mask bookkeeping for
-// every kind present, which mixed traffic (config C) pays on every wave.
-#ifndef EMURX_FLATRES
-#define EMURX_FLATRES 0
-#endif
-__device__ __forceinline__ bool any_lane(bool c) { return __ballot(c) != 0; }
-template <class Flow, class Dmac>
-__device__ __forceinline__ void resolve_done_flat(const emurx_dev_tables& T, Rec& r, const LKey& k, const Probe& p,
-                                                  const Bucket& ce, Flow flow, Dmac dmac) {
-    const uint32_t cb = r.proto, plug = cb_plugin(cb), key = k.key;
-    const uint32_t w0 = r.vport, w1 = r.vlan0, w2 = r.vlan1;
-    // ---- first buckets, every view at once ----
-    uint2 nsr = make_uint2(EMURX_ID_NONE, 0), mc = make_uint2(EMURX_ID_NONE, 0);
-    IpHit i4{EMURX_ID_NONE, 0, 0}, i6{EMURX_ID_NONE, 0, 0};
-    bool nhole = false, mhole = false, h4 = false, h6 = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint4 x = p.ne.s[j];
-        nhole |= x.w == EMURX_EMPTY;
-        if (x.w != EMURX_EMPTY && (x.x & 0xffffu) == w0 && x.y == w1 && x.z == w2) nsr = make_uint2(x.w, x.x >> 16);
-    }
-    const bool isMac = key == kMac || key == kEui, isIp4 = key == kIp4, isIp6 = key == kIp6;
-    // the client views compare the Namespace id found above; a view no lane of the wave needs
-    // is skipped (wave-uniform tests: a wave of one key kind computes one view)
-    if (any_lane(isMac)) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint4 y = ce.s[j];
-            mhole |= y.w == EMURX_EMPTY;
-            if (y.w != EMURX_EMPTY && y.x == nsr.x && y.y == p.mlo && (y.z & 0xffffu) == p.mhi) mc = make_uint2(y.w, y.z >> 16);
-        }
-    }
-    if (any_lane(isIp4 || isIp6)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint4 x = ce.s[2 * j], y = ce.s[2 * j + 1];
-            h4 |= y.w == EMURX_EMPTY;
-            h6 |= y.w == EMURX_EMPTY;
-            if (y.w != EMURX_EMPTY && x.x == nsr.x && x.y == k.kw[0]) i4 = IpHit{y.w, x.z, x.w};
-            if (y.w != EMURX_EMPTY && x.x == nsr.x && x.y == k.kw[0] && x.z == k.kw[1] && x.w == k.kw[2] && y.x == k.kw[3])
-                i6 = IpHit{y.w, y.y, y.z};
-        }
-    }
-    // ---- chains past the first buckets (wave-uniform test; the loop resolvers walk on) ----
-    const bool ns_more = nsr.x == EMURX_ID_NONE && !nhole;
-    if (any_lane(ns_more) && ns_more) {
-        const uint32_t b = (p.nb + 1) & T.ns_mask;
-        nsr = resolve_ns(T, b, ld_bucket(T.ns_tab, b), w0, w1, w2);
-    }
-    const uint32_t ns = nsr.x;
-    // the client probe needs the Namespace id: a lane whose Namespace came from its chain, or
-    // whose client key lies past the first bucket, resolves its client from the start again
-    const bool c_more = ns != EMURX_ID_NONE && (nsr.y & (1u << plug)) &&
-                        (ns_more || (isMac && mc.x == EMURX_ID_NONE && !mhole) ||
-                         (isIp4 && i4.cid == EMURX_ID_NONE && !h4) || (isIp6 && i6.cid == EMURX_ID_NONE && !h6));
-    if (any_lane(c_more) && c_more) {
-        if (isMac) mc = resolve_mac(T, p.cbk, ce, ns, p.mlo, p.mhi);
-        else if (isIp4) i4 = resolve_ip4(T, p.cbk, ce, ns, k.kw[0]);
-        else if (isIp6) i6 = resolve_ip6(T, p.cbk, ce, ns, k.kw);
-    }
-    // ---- the rule's client, by selects ----
-    uint32_t cid = EMURX_ID_NONE, cpl = 0, clo = 0, chi = 0;
-    bool check = true;
-    if (isMac) { cid = mc.x; cpl = mc.y; clo = p.mlo; chi = p.mhi; }
-    if (isIp4) { cid = i4.cid; cpl = i4.mhip >> 16; clo = i4.mlo; chi = i4.mhip & 0xffffu; }
-    if (isIp6) { cid = i6.cid; clo = i6.mlo; chi = i6.mhip & 0xffffu; }
-    const bool icmp4 = isIp4 && cb != EMURX_CB_ARP;
-    const uint3 dm = dmac();
-    if (icmp4 && !(clo == dm.x && chi == dm.y)) cid = EMURX_ID_NONE;  // IsUnicastToMe
-    check = !(icmp4 || key == kEui || isIp6);
-    const bool ns_ok = ns != EMURX_ID_NONE && (nsr.y & (1u << plug));
-    // GetFirstClient (dhcpsrv / eapol) and the EUI-64 RA-prefix check read client info
-    const bool first = ns_ok && key == kFirst;
-    const bool eui = ns_ok && key == kEui && cid != EMURX_ID_NONE && !(k.kw[0] == 0x000080feu && k.kw[1] == 0);
-    if (any_lane(first || eui)) {
-        if (first) cid = gld4(T.ns_info + 4 * ns + 1);
-        if (first || eui) {
-            const CInfo c = client_info(T, cid);
-            cpl = c.plugins;
-            if (eui && !((c.ra & 1u) && ((c.ra >> 8) & 0xff) == 64 && c.ra0 == k.kw[0] && c.ra1 == k.kw[1]))
-                cid = EMURX_ID_NONE;
-        }
-    }
-    if ((key == kEui || isIp6) && cid != EMURX_ID_NONE && (!(clo == dm.x && chi == dm.y) || dm.z)) cid = EMURX_ID_NONE;
-    // ---- the outcome ----
-    uint32_t lk = cid == EMURX_ID_NONE ? EMURX_LK_NO_CLIENT
-                  : (check && !(cpl & (1u << plug))) ? EMURX_LK_CLIENT_NO_PLUGIN : EMURX_LK_CLIENT;
-    if (key == kNsLevel) lk = EMURX_LK_NS_LEVEL;
-    if (key == kNoClient) lk = EMURX_LK_NO_CLIENT;
-    if (!(nsr.y & (1u << plug))) lk = EMURX_LK_NS_NO_PLUGIN;
-    if (ns == EMURX_ID_NONE) lk = EMURX_LK_NO_NS;
-    if (ns != EMURX_ID_NONE) r.ns = ns;
-    const bool client_kind = ns_ok && key != kNsLevel && key != kNoClient;
-    if (client_kind && cid != EMURX_ID_NONE) r.cl = cid;
-    set_lk(r, lk);
-    // transport: the client's TransportCtx decides (plugin_transport.go:109-114, :73-80)
-    const bool trans = key == kMac && (cb == EMURX_CB_TCP || cb == EMURX_CB_UDP) && lk == EMURX_LK_CLIENT;
-    if (trans) r.flow = EMURX_FLOW_NO_CTX;
-    if (T.ft_on && any_lane(trans) && trans && (cpl & EMURX_CPL_CTX)) r.flow = flow(cid);
-}
-
 // GetNs + the callback's client rule against the tables (both bucket reads in flight together)
 template <class Flow, class Dmac>
 __device__ __forceinline__ void resolve(const emurx_dev_tables& T, Rec& r, const LKey& k, Flow flow, Dmac dmac) {
     const Probe p = probe_issue(T, r, k);
     Bucket ce{};
     if (p.ctab) ce = ld_bucket(p.ctab, p.cbk);
-#if EMURX_FLATRES == 2
-    // hybrid: a wave whose lanes share one key kind takes the switch without divergence
-    if (__ballot(k.key != (uint32_t)__builtin_amdgcn_readfirstlane((int)k.key)) == 0)
-        resolve_done(T, r, k, p, ce, flow, dmac);
-    else
-        resolve_done_flat(T, r, k, p, ce, flow, dmac);
-#elif EMURX_FLATRES
-    resolve_done_flat(T, r, k, p, ce, flow, dmac);
-#else
     resolve_done(T, r, k, p, ce, flow, dmac);
-#endif
 }
 template <class Flow>
 __device__ __forceinline__ void resolve(const emurx_dev_tables& T, Rec& r, const LKey& k, Flow flow) {

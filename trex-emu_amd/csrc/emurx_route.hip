@@ -47,16 +47,7 @@ __global__ __launch_bounds__(kBlock) void k_route(const emurx_rec* __restrict__ 
     const uint32_t d = a.x != EMURX_ID_NONE ? emurx_owner(emurx_tk_hash(b.x & 0xffffu, a.z, a.w), n_parts) : 0xffu;
     if (kPack && wv == 0)  // this tile's offset: group offset + the group's earlier tiles
         tile_offsets(tile_cnt, grp_off, n_parts, tile, lane, s_toff);
-    uint32_t rank = 0;
-    uint64_t left = __ballot(d != 0xffu);
-    while (left) {
-        const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1;
-        const uint32_t dd = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)lead);
-        const uint64_t m = __ballot(d == dd);
-        if (d == dd) rank = mbcnt(m);
-        if (lane == lead) s_wcnt[wv][dd] = (uint32_t)__popcll(m);
-        left &= ~m;
-    }
+    const uint32_t rank = wave_rank_by_id(d, d != 0xffu, lane, s_wcnt[wv]);
     __syncthreads();
     if (!kPack) {
         if (tid < 16) {
@@ -146,17 +137,12 @@ __global__ __launch_bounds__(kScanThreads) void k_route_scan(uint32_t* __restric
 // descriptors (the production path: the device framing walk keys them) read no frame byte, and
 // the kernel falls 10.7 -> 8.0 us per 2M frames; unkeyed waves wider than 2 KiB gather instead
 // (config D unkeyed: 39.2 -> 46.6 us; DESIGN.md §6 round 4, profiles/r04/ab_owner_count/)
-#ifndef EMURX_OC_STAGE
-#define EMURX_OC_STAGE 2048
-#endif
-// Tiles per workgroup: every tile's descriptors are loaded at the top (EMURX_OC_TPW loads in
+constexpr uint32_t kOcStage = 2048;
+// Tiles per workgroup: every tile's descriptors are loaded at the top (kOcTpw loads in
 // flight per lane), the tiles then counted one after the other, and the workgroup's counts
-// added to its group once (its tiles share one group of 64)
-#ifndef EMURX_OC_TPW
-#define EMURX_OC_TPW 1
-#endif
-constexpr uint32_t kOcStage = EMURX_OC_STAGE;
-constexpr uint32_t kOcTpw = EMURX_OC_TPW;
+// added to its group once (its tiles share one group of 64).  The loop over one tile stays:
+// written for a single tile the kernel compiles to other code (its `k >= tn` guard goes).
+constexpr uint32_t kOcTpw = 1;
 static_assert(kOcTpw >= 1 && kGroup % kOcTpw == 0, "a workgroup's tiles in one group");
 __global__ __launch_bounds__(kBlock) void k_owner_count(const uint8_t* __restrict__ frames,
                                                         const emurx_desc* __restrict__ desc, uint32_t n,
@@ -238,14 +224,7 @@ __global__ __launch_bounds__(kBlock) void k_owner_count(const uint8_t* __restric
             l2_vlans(len, b12, b16, v0, v1);
             d = emurx_owner(emurx_tk_hash(vport, v0, v1), n_parts);
         }
-        uint64_t left = __ballot(d != 0xffu);
-        while (left) {
-            const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1;
-            const uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)lead);
-            const uint64_t m = __ballot(d == q);
-            if (lane == lead) s_wcnt[wv][q] = (uint32_t)__popcll(m);
-            left &= ~m;
-        }
+        wave_rank_by_id(d, d != 0xffu, lane, s_wcnt[wv]);  // the counts alone
         __syncthreads();
         if (tid < 16) {
             const uint32_t c = s_wcnt[0][tid] + s_wcnt[1][tid] + s_wcnt[2][tid] + s_wcnt[3][tid];
@@ -289,13 +268,7 @@ __global__ __launch_bounds__(kBlock) void k_desc_keys(const uint8_t* __restrict_
 // The heads are read once: non-temporal LDS-DMA (aux nt); the outputs are stored write-through
 // (sc1), so their lines leave this XCD's L2 to the table lines the probes re-read (round 5:
 // config D's partitioned step +1.3 %, k_lookup 111 -> 108 us in the phase times,
-// profiles/r05/ab_lookup/).  EMURX_LOOKUP_NT=0: the default policies
-#ifndef EMURX_LOOKUP_NT
-#define EMURX_LOOKUP_NT 1
-#endif
-#ifndef EMURX_LOOKUP_WPE
-#define EMURX_LOOKUP_WPE 6
-#endif
+// profiles/r05/ab_lookup/).
 template <class Flow>
 __device__ __forceinline__ void resolve_owner(const emurx_dev_tables& T, Rec& r, LKey k, uint32_t chash, uint4 kw6,
                                               Flow flow) {
@@ -335,7 +308,8 @@ __device__ __forceinline__ void resolve_owner(const emurx_dev_tables& T, Rec& r,
     }
     resolve_done(T, r, k, p, ce, flow);
 }
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMURX_LOOKUP_WPE))) void k_lookup(const uint8_t* __restrict__ recv,
+constexpr int kLookupWpe = 6;  // waves per SIMD the compiler budgets k_lookup's registers for
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kLookupWpe))) void k_lookup(const uint8_t* __restrict__ recv,
                                                    const uint32_t* __restrict__ recv_count, uint32_t n_parts,
                                                    uint32_t cap, uint32_t tcap, emurx_dev_tables T,
                                                    emurx_route_rec* __restrict__ out, uint32_t* __restrict__ flow) {
@@ -355,7 +329,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMURX_LO
         if (k * kWave + lane < nvec)
             __builtin_amdgcn_global_load_lds(base + k * kWave + lane,
                                              (__attribute__((address_space(3))) void*)&s_rec[wv][k * kWave], 16, 0,
-                                             EMURX_LOOKUP_NT ? 2 : 0);
+                                             2);
     wait_vm0();
     wave_lds_sync();
     const bool live = idx < cnt;
@@ -402,15 +376,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMURX_LO
     const uint32_t npieces = min(kWave, cnt - idx0) * 5;
 #pragma unroll
     for (uint32_t k5 = 0; k5 < 5; ++k5)
-        if (k5 * kWave + lane < npieces) {
-#if EMURX_LOOKUP_NT
+        if (k5 * kWave + lane < npieces)
             __hip_atomic_store(reinterpret_cast<unsigned long long*>(o) + k5 * kWave + lane,
                                reinterpret_cast<const unsigned long long*>(park)[k5 * kWave + lane], __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);  // sc1: the line leaves this XCD's L2
-#else
-            o[k5 * kWave + lane] = park[k5 * kWave + lane];
-#endif
-        }
     if (flow && live) flow[j] = r.flow;
 }
 
@@ -446,15 +415,13 @@ int emurx_launch_lookup(const emurx_lookup_rec* recv, const uint32_t* recv_count
     using namespace emurx;
     if (!n_parts || !cap) return 0;
     if (n_parts > 65535) return -1;
-// k_lookup's occupancy is capped at 4 workgroups (16 waves) per CU by unused LDS: its 10 KiB of
-// record rows + 30 KiB = 40 KiB of the CU's 160 KiB.  Its probes are random table lines; more
-// waves in flight only queue more of them, and beside the next batch's k_rx<2> on the other
-// stream the freed slots serve that kernel (6 workgroups 98.4 us per 2M records,
-// 4: 96.9 us, the pipelined partitioned step +3-4.5 %; at an owner of 8, 74.3 -> 72.3 us)
-#ifndef EMURX_LOOKUP_LDS_PAD
-#define EMURX_LOOKUP_LDS_PAD (30 * 1024)
-#endif
-    return EMURX_HIP_OK(emurx_launch(k_lookup, dim3((cap + kBlock - 1) / kBlock, n_parts), dim3(kBlock), EMURX_LOOKUP_LDS_PAD, st,
+    // k_lookup's occupancy is capped at 4 workgroups (16 waves) per CU by unused LDS: its 10 KiB
+    // of record rows + 30 KiB = 40 KiB of the CU's 160 KiB.  Its probes are random table lines;
+    // more waves in flight only queue more of them, and beside the next batch's k_rx<2> on the
+    // other stream the freed slots serve that kernel (6 workgroups 98.4 us per 2M
+    // records, 4: 96.9 us, the pipelined partitioned step +3-4.5 %; at an owner of 8, 74.3 -> 72.3 us)
+    constexpr uint32_t kLookupLdsPad = 30 * 1024;
+    return EMURX_HIP_OK(emurx_launch(k_lookup, dim3((cap + kBlock - 1) / kBlock, n_parts), dim3(kBlock), kLookupLdsPad, st,
                                      reinterpret_cast<const uint8_t*>(recv), recv_count, n_parts, cap, tcap, T, out, flow))
                ? 0
                : -1;

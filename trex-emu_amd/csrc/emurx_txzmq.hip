@@ -30,9 +30,6 @@ namespace emurx {
 constexpr uint32_t kTxTile = 64;  // frames per wave; == EMURX_ZMQ_TX_BURST
 static_assert(kTxTile == EMURX_ZMQ_TX_BURST && kTxTile == kWave, "one burst per wave");
 
-#ifndef EMURX_TXC_NOUP
-#define EMURX_TXC_NOUP 0
-#endif
 // end(i) - i for lane i of the tile at `base`, from this tile's and the next tile's lengths
 __device__ __forceinline__ uint32_t tx_endrel_v(uint32_t len, uint32_t lb, uint32_t n, uint32_t base, uint32_t* q) {
     const uint32_t lane = lane_id();
@@ -280,12 +277,6 @@ __global__ __launch_bounds__(kTxUnitWaves * kWave) void k_txz_chain(const emurx_
     uint32_t up = p;
     for (uint32_t k = 1;; ++k) {
         const bool top = k == c.L - 1;
-#if EMURX_TXC_NOUP
-        if (!top) {  // timing of the leaf + level-1 compose alone (wrong results past one level)
-            tx_compose_rows(c, k, up, cn, S);
-            return;
-        }
-#endif
         const uint32_t par = up >> 6, kids = top ? 0u : min(c.units[k] - par * 64, 64u);
         if (!top) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sc1 stores of T / B
@@ -332,14 +323,6 @@ __device__ __forceinline__ void tx_tile_base(const TxChain& c, uint32_t t, uint3
 }
 
 constexpr uint32_t kTxSlow = 512;  // long-frame tiles: rows assembled byte by byte, listed per wave
-// Waves per tile of the long variant (EMURX_TXZ_LONG), A/B knob: split, every wave makes the
-// tile's segments itself and copies a contiguous part of its rows.  Measured on config E (1M
-// IMIX frames): 1 wave 263 us per call, 2 waves 262-268, 4 waves 288:
-// the launch's tail is not what E's write pays for.  1 (one wave per tile) kept.
-#ifndef EMURX_TX_SPLIT
-#define EMURX_TX_SPLIT 1
-#endif
-constexpr uint32_t kTxSplit = EMURX_TX_SPLIT;
 
 // OR a little-endian word v into LDS bytes [p, p + 4) (dwords at p >> 2 and the next one)
 __device__ __forceinline__ void lds_or4(uint32_t* o32, uint32_t p, uint32_t v) {
@@ -367,10 +350,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
     __shared__ __attribute__((aligned(16))) uint32_t s_img[4][kLds / 4];
     __shared__ uint32_t s_q[4][2 * kWave];
     const uint32_t wv = threadIdx.x / kWave, lane = lane_id();
-    // the long variant (no image): kTxSplit waves per tile, each making the tile's segments itself
-    // and copying its share of the tile's rows
-    constexpr uint32_t kSplit = kTxImg == 0 ? kTxSplit : 1u;
-    const uint32_t gw = blockIdx.x * 4 + wv, t = gw / kSplit, part = gw % kSplit;
+    // One wave per tile, the long variant (EMURX_TXZ_LONG) too.  Several waves per tile, each
+    // making the tile's segments itself and copying a contiguous part of its rows, measured on
+    // config E (1M IMIX frames): 1 wave 263 us per call, 2 waves 262-268, 4 waves 288 (DESIGN.md
+    // §6 round 6): the launch's tail is not what E's write pays for.
+    const uint32_t t = blockIdx.x * 4 + wv;
     if (t >= ntiles) return;  // wave-uniform
     const uint32_t base = t * kTxTile;
     // loads that wait on nothing first: this and the next tile's descriptors, the tile base
@@ -507,20 +491,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
         out[x] = (uint8_t)byte_at((uint32_t)y, kk);
     };
     uint32_t nslow = 0, k = 0;
-#ifndef EMURX_TX_P2ROUND  // 0: the slow rows after the tile's last round (rounds 1-4)
-#define EMURX_TX_P2ROUND 1
-#endif
-#if EMURX_TX_P2ROUND
     uint32_t p2done = 0;
-#endif
-#ifndef EMURX_TX_KU
-#define EMURX_TX_KU 4
-#endif
-    constexpr uint32_t kU = EMURX_TX_KU;  // rows per lane per round, their loads in flight together
-    // this wave's share of the rows: kSplit contiguous parts, whole 64-row groups each
-    const uint32_t per = kSplit == 1 ? nrow : ((nrow + kSplit - 1) / kSplit + kWave - 1) & ~(kWave - 1);
-    const uint32_t rbeg = min(nrow, part * per), rend = min(nrow, rbeg + per);
-    for (uint32_t r0 = rbeg; r0 < rend; r0 += kU * kWave) {  // wave-uniform trip count
+    constexpr uint32_t kU = 4;  // rows per lane per round, their loads in flight together
+    for (uint32_t r0 = 0; r0 < nrow; r0 += kU * kWave) {  // wave-uniform trip count
         uint4 cur[kU], nxt[kU];
         uint32_t sh[kU], kk[kU];
         bool fast[kU];
@@ -531,22 +504,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
             kk[u] = k;
             cur[u] = nxt[u] = make_uint4(0, 0, 0, 0);
             sh[u] = 0;
-#ifdef EMURX_TX_PURECOPY  // timing only: every row a copy from the frames buffer's first 256 MiB
-            if (r < rend && xb + 16ull * r + 16 <= cap) {
-#ifndef EMURX_TX_PC_OFF
-#define EMURX_TX_PC_OFF 5
-#endif
-                const uintptr_t sa = (uintptr_t)(frames + (((uint32_t)xb + 16 * r) & 0x0ffffff0u) + EMURX_TX_PC_OFF);
-                const uint4* sv = reinterpret_cast<const uint4*>(sa & ~(uintptr_t)15);
-                sh[u] = EMURX_TX_PC_OFF;
-                cur[u] = sv[0];
-                if (EMURX_TX_PC_OFF) nxt[u] = sv[1];
-                fast[u] = true;
-            }
-            if (false) {
-#else
-            if (r < rend) {
-#endif
+            if (r < nrow) {
                 const int y0 = (int)(16 * r) - (int)head;
                 const uint32_t yc = y0 < 0 ? 0u : (uint32_t)y0;
                 while (k < last && sg[0][k + 1] <= yc) ++k;
@@ -577,7 +535,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
                 }
                 *reinterpret_cast<uint4*>(out + xb + 16ull * r) = make_uint4(o[0], o[1], o[2], o[3]);
             }
-            const bool slw = r < rend && !fast[u];
+            const bool slw = r < nrow && !fast[u];
             const uint64_t m = __ballot(slw);
             const uint32_t at = nslow + mbcnt(m);
             if (slw) {
@@ -586,7 +544,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
             }
             nslow += (uint32_t)__popcll(m);
         }
-#if EMURX_TX_P2ROUND && !defined(EMURX_TX_NOPASS2)
         // this round's byte-by-byte rows now, while the lines its full rows wrote are in L2 (a
         // line left partly written costs its write-back a read-modify-write)
         wave_lds_sync();
@@ -596,19 +553,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
             row_byte(e >> 6, i & 15, e & 63);
         }
         p2done = nl;
-#endif
     }
     wave_lds_sync();
-#ifdef EMURX_TX_NOPASS2  // timing only: the long path without its byte-by-byte rows (wrong output)
-    const uint32_t nb = 0;
-#else
     const uint32_t nb = min(nslow, kTxSlow) * 16;
-#endif
-#if EMURX_TX_P2ROUND
     for (uint32_t i = p2done * 16 + lane; i < nb; i += kWave) {
-#else
-    for (uint32_t i = lane; i < nb; i += kWave) {
-#endif
         const uint32_t e = slow[i >> 4];
         row_byte(e >> 6, i & 15, e & 63);
     }
@@ -667,11 +615,10 @@ int emurx_launch_tx_zmq(const uint8_t* frames, const emurx_desc* desc, uint32_t 
     const uint32_t nt = c.ntiles;
     hipError_t e = emurx_launch(k_txz_chain, dim3(c.units[1]), dim3(kTxUnitWaves * kWave), 0, st, desc, c);
     if (e == hipSuccess) {
-        const uint32_t waves = variant == EMURX_TXZ_LONG ? nt * kTxSplit : nt;  // the long variant: kTxSplit waves per tile
         e = emurx_launch(variant == EMURX_TXZ_NARROW ? k_txz_emit<kTxImgNarrow>
                          : variant == EMURX_TXZ_LONG ? k_txz_emit<0>
                                                      : k_txz_emit<kTxImgWide>,
-                         dim3((waves + 3) / 4), dim3(256), 0, st, frames, desc, n, nt, c, out, (unsigned long long)cap, mo);
+                         dim3((nt + 3) / 4), dim3(256), 0, st, frames, desc, n, nt, c, out, (unsigned long long)cap, mo);
     }
     return EMURX_HIP_OK(e) ? 0 : -1;
 }

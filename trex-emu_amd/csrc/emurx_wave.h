@@ -48,6 +48,24 @@ __device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// a lane's rank among the `in` lanes that hold its id (the lanes below it), and every present
+// id's lane count into cnt[id], written by that id's first lane: one iteration of scalar
+// bookkeeping per distinct id present.  A lane that is not `in` carries an id that no `in` lane
+// has (the callers pass 0xff) and gets rank 0.  Called converged.
+__device__ __forceinline__ uint32_t wave_rank_by_id(uint32_t id, bool in, uint32_t lane, uint32_t* cnt) {
+    uint32_t rank = 0;
+    uint64_t left = __ballot(in);
+    while (left) {
+        const uint32_t lead = (uint32_t)__ffsll((long long)left) - 1;
+        const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)lead);
+        const uint64_t m = __ballot(id == g);
+        if (id == g) rank = mbcnt(m);
+        if (lane == lead) cnt[g] = (uint32_t)__popcll(m);
+        left &= ~m;
+    }
+    return rank;
+}
+
 // wave64 reductions on the DPP network (quad perms, row rotates, row broadcasts; result is
 // read from lane 63 into a scalar register): no LDS traffic, 6 VALU + 1 readlane
 template <int kCtrl, int kRowMask = 0xf>
