@@ -525,7 +525,10 @@ int emurx_ingest_stream(emurx_t* h, uint32_t slot, void** stream);
                    (MLD reports behind a hop-by-hop header, ipv6/mld.go:1271)
      ICMP4         ICMPv4Header(p[l4:]).UpdateChecksum()                      icmp4.go:252-256
    A frame whose header or field would lie past `len` (the Go slices panic there) is left
-   untouched and gets status EMURX_TX_RANGE. */
+   untouched and gets status EMURX_TX_RANGE; so does a kind that is none of the six.  The IPv4
+   header slice is IHL * 4 bytes and never fewer than the 20 every caller takes.
+   `len` up to 65535 is accepted (an L4 span that long is summed exactly).  The frames of one
+   call must not overlap: each is rewritten independently of the others, in no given order. */
 #define EMURX_TX_IPV4_HDR 0x01u
 #define EMURX_TX_V6_NH 0x02u
 #define EMURX_TX_L4_SHIFT 4
