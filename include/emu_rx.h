@@ -474,7 +474,9 @@ typedef struct emurx_ingest_result {
     uint32_t qoff[EMURX_NUM_QUEUES + 1];
     emurx_counters delta;        /* ParserStats + VethStats deltas of the batch             */
     uint32_t one_launch;         /* 1: the batch ran as one kernel (k_ingest_small, the
-                                    small-batch path), 0: the copy + four-launch pipeline     */
+                                    small-batch path), 0: the copy + four-launch pipeline (always
+                                    with answers on, emurx_ingest_set_answers: the one-launch path
+                                    never brings the frames into device memory)              */
     uint32_t degraded;           /* 1: a one-launch batch whose workgroups did not all arrive
                                     within the wait bound (EMURX_INGEST_SPIN_US, default 200 us,
                                     read at emurx_open, plus 0.1 ns per byte of the batch's
@@ -486,8 +488,8 @@ typedef struct emurx_ingest_result {
    (grown on demand; not while the slot has a batch in flight). */
 int emurx_ingest_buffer(emurx_t* h, uint32_t slot, size_t bytes, uint8_t** buf);
 /* Enqueue the slot's messages.  EMURX_ENOSPC when the messages could announce more frames
-   than cfg.max_frames (split the batch); EMURX_EINVAL for a message outside the buffer or a
-   slot still in flight. */
+   than cfg.max_frames (split the batch) or, with answers on (emurx_ingest_set_answers), end past
+   cfg.max_bytes; EMURX_EINVAL for a message outside the buffer or a slot still in flight. */
 int emurx_ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nmsg);
 /* Wait for the slot's batch and point `res` at its results (library-owned pinned memory). */
 int emurx_ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res);
@@ -579,6 +581,22 @@ int emurx_tx_checksum_dev(emurx_t* h, uint8_t* d_frames, const emurx_tx_desc* d_
 #define EMURX_TX_ZMQ_MAX_FRAMES (1u << 26) /* n must be below it (else EMURX_EINVAL)       */
 int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n,
                      uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off, uint64_t* d_info, void* stream);
+/* The same framing with the frame count taken from device memory: the first min(*d_count, n_max)
+   descriptors are framed exactly as emurx_tx_zmq_dev with that n would frame them (d_out,
+   d_msg_off[0 .. n_msgs] and d_info).  *d_count (u64, 8-byte aligned) is read on the device when
+   the kernels run, so a call enqueued behind the responder on the same stream takes d_count =
+   the responder's d_info (word 0: replies written) and no host synchronisation sits between the
+   two.  Descriptors at or past the count are never read (the responder leaves them
+   unspecified), nor are the frames they would name.  d_msg_off has capacity n_max + 1; words
+   past d_msg_off[n_msgs] are left as they were.  out_cap as above for the counted frames.
+   n_max >= EMURX_TX_ZMQ_MAX_FRAMES, a NULL d_count, or the alignments above are EMURX_EINVAL;
+   n_max == 0 writes a zero d_info and d_msg_off[0] = 0.  Two launches of n_max's size on
+   `stream`, no host synchronisation; the same scratch and the same "must not overlap" rule as
+   emurx_tx_zmq_dev.  The write's LDS image is the one the plain calls last chose; a counted
+   call samples no feedback for that choice. */
+int emurx_tx_zmq_counted_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                             uint32_t n_max, const uint64_t* d_count,
+                             uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off, uint64_t* d_info, void* stream);
 
 /* ---- the stateless answers on the device ------------------------------------------------
    Three of the plugins' answers are a pure function of the frame and of a table the device
@@ -881,6 +899,62 @@ int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
                      const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome,
                      emurx_nsstat_ev* d_ev, uint32_t ev_cap,
                      uint8_t* d_done, uint64_t* d_info, void* stream);
+
+/* ---- the device answers on an ingest slot ---------------------------------------------------
+   The batched ingest keeps a batch's frames, descriptors and records private to its slot, so a
+   caller without device memory cannot hand them to the four calls above.  With answers on, a
+   slot runs them itself: after k_rx and the queue pack, on the slot's stream,
+     1. emurx_respond_kinds_dev(kinds) over the slot's frames, descriptors and records (holes are
+        EMURX_DESC_HOLE descriptors, which every stage skips), with an out_cap no batch can exceed
+        (below), so EMURX_RSP_NOSPC does not occur;
+     2. emurx_tx_zmq_counted_dev over the replies, d_count = the responder's d_info;
+     3. emurx_learn_dev with ARP and / or ND as `kinds` selects them (neither: no learn call, every
+        learn outcome EMURX_LRN_NONE), ev_cap = emurx_learn_max_events(h): it cannot overflow;
+     4. emurx_nsstat_dev(kinds) with ev_cap = emurx_nsstat_max_events(h);
+   then one launch (k_ans_out) that reads the stages' counts on the device and writes what was
+   produced, and no more, into pinned host memory; the three per-frame byte arrays ride the
+   batch's one result copy.  No host synchronisation between submit and wait; a batch with no
+   reply and no event moves a few hundred bytes more than one without answers.
+   emurx_ingest_set_answers(h, slot, kinds) holds for the slot's later submits; kinds: EMURX_RSPK_*
+   bits, 0 = off (the default).  A slot with a batch in flight, slot >= EMURX_INGEST_SLOTS or a
+   bit above EMURX_RSPK_ALL are EMURX_EINVAL; a host-only handle EMURX_EDEVICE.  The first call
+   with kinds != 0 allocates everything the chain needs for cfg.max_frames and cfg.max_bytes (it
+   waits for the device once, and grows the handle's framing and responder scratch to
+   max_frames), so that no submit allocates or synchronises for it.  The sizes follow from the
+   stages' rules: an answered or learned frame is at least 42 bytes long, so a batch has at most
+   max_bytes / 42 replies and learn events; align16(reply) <= len + 54, so the replies take at
+   most max_bytes * 96 / 42 bytes and their messages 8 bytes per reply more.  With answers on,
+   emurx_ingest_submit returns EMURX_ENOSPC for messages that end past cfg.max_bytes.
+   A batch submitted with answers on always takes the copy + launches pipeline:
+   res.one_launch is 0, because the one-launch path never brings the frames into device memory.
+   emurx_ingest_wait is unchanged.  emurx_ingest_answers(h, slot, &out), after the
+   emurx_ingest_wait of that batch, points `out` at library-owned memory, valid until the slot's
+   next submit; frame indices (reply_src, the events' first / last, the per-frame arrays) are in
+   res.rec's numbering, also when messages fell short of the frames they announced.  It returns
+   EMURX_ENOENT when the slot's last batch ran without answers, EMURX_EINVAL before any wait or
+   with a batch in flight.
+   The four stages' scratch belongs to the handle: the answer stages of different slots run one
+   after another (each waits for the previous one's event; parse and classify of different slots
+   still overlap), and a caller's own emurx_respond_dev / emurx_respond_kinds_dev /
+   emurx_learn_dev / emurx_nsstat_dev / emurx_tx_zmq_dev / emurx_tx_zmq_counted_dev calls must not
+   overlap a slot's batch that has answers on.  INTEGRATION.md has the loop. */
+typedef struct emurx_answers {
+    const uint8_t* tx;            /* the replies as ZMQ messages, back to back (emurx_tx_zmq_dev's layout) */
+    const uint64_t* tx_msg_off;   /* [n_tx_msgs + 1] message starts in tx, then tx_bytes */
+    uint32_t n_tx_msgs, n_replies;
+    uint64_t tx_bytes;
+    const uint32_t* reply_src;    /* [n_replies] rx frame index of each reply, res.rec numbering */
+    const uint8_t* rsp_outcome;   /* [n_frames] enum emurx_rsp */
+    const uint8_t* lrn_outcome;   /* [n_frames] enum emurx_lrn (all 0 when kinds has neither ARP nor ND) */
+    const uint8_t* done;          /* [n_frames] emurx_nsstat_dev's d_done */
+    const emurx_learn_ev* learn_ev;  /* [n_learn] ascending `last` */
+    uint32_t n_learn;
+    const emurx_nsstat_ev* ns_ev;    /* [n_ns] ascending ns_id */
+    uint32_t n_ns;
+    uint64_t rsp_info[EMURX_RSP_INFO_WORDS], lrn_info[EMURX_LRN_INFO_WORDS], nss_info[EMURX_NSS_INFO_WORDS];
+} emurx_answers;               /* 352 bytes */
+int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds);
+int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out);
 
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);

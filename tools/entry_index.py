@@ -32,7 +32,8 @@ GROUPS = [
      "(device image of the maps above)"),
     ("Mid-batch mutations", ["emurx_table_gen", "emurx_recs_stale"], "DESIGN.md §2.2, `dhcp.go:718`"),
     ("Batched ingest (primary)", ["emurx_ingest_buffer", "emurx_ingest_submit", "emurx_ingest_wait",
-                                  "emurx_ingest_stream", "emurx_zmq_walk_dev"],
+                                  "emurx_ingest_stream", "emurx_ingest_set_answers", "emurx_ingest_answers",
+                                  "emurx_zmq_walk_dev"],
      "`VethIFZmq.OnRxStream` over the rx `select` loop's messages, `thread_ctx.go:409-410`, `veth_zmq.go:277-320`"),
     ("Receive path (device-resident; per-message fallback)",
      ["emurx_classify_dev", "emurx_parse_dev", "emurx_rx_stream", "emurx_zmq_descriptors",
@@ -47,7 +48,7 @@ GROUPS = [
       "emurx_group_start", "emurx_group_end", "emurx_exchange_dev"],
      "no Go counterpart: the single goroutine's `MapNsT` (`thread_ctx.go:139,397-419,772-784`) split by owner "
      "(SURVEY §8e)"),
-    ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev"],
+    ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev", "emurx_tx_zmq_counted_dev"],
      "gopacket checksum updates; `VethIFZmq.Send/FlushTx` `veth_zmq.go:149-200`"),
     ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev"],
      "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`, "

@@ -115,8 +115,30 @@ struct IngestSlot {
     uint32_t seq = 0;
     bool small = false;       // the batch in flight took the small path
     std::vector<uint32_t> remap;          // slot -> frame index, only when a message fell short
+    // answers (emurx_ingest_set_answers): the chain's outputs, sized once for cfg.max_frames /
+    // cfg.max_bytes; the per-frame outcome arrays join the result block (set_results)
+    uint32_t ans_kinds = 0;               // the setting for later submits (EMURX_RSPK_*, 0: off)
+    uint32_t ans_batch = 0;               // the kinds of the batch in flight / last waited for
+    bool waited = false;                  // a batch has been waited for
+    uint64_t ans_rsp_cap = 0, ans_tx_cap = 0;
+    uint32_t ans_r_cap = 0, ans_ev_cap = 0, ans_ns_cap = 0;
+    DevBuf<uint8_t> d_rsp_out, d_tx;
+    DevBuf<emurx_desc> d_rsp_desc;
+    DevBuf<uint32_t> d_rsp_src;
+    DevBuf<uint64_t> d_tx_off, d_ainfo;   // d_ainfo: rsp, lrn, nss and tx info, as the answer block's head
+    DevBuf<emurx_learn_ev> d_lev;
+    DevBuf<emurx_nsstat_ev> d_nsev;
+    View<uint8_t> d_rspo, d_lrno, d_donef, h_rspo, h_lrno, h_donef;  // [n] in the result block
+    PinBuf<uint8_t> h_ans;                // the pinned answer block (k_ans_out writes it)
+    View<uint64_t> h_ahead, h_tx_off;
+    View<uint8_t> h_tx;
+    View<uint32_t> h_src;
+    View<emurx_learn_ev> h_lev;
+    View<emurx_nsstat_ev> h_nsev;
     void release() {
         if (st) (void)hipStreamSynchronize(st);
+        d_rsp_out.release(); d_tx.release(); d_rsp_desc.release(); d_rsp_src.release(); d_tx_off.release();
+        d_ainfo.release(); d_lev.release(); d_nsev.release(); h_ans.release();
         d_qseg.release(); d_tcnt.release(); d_ticket.release(); d_hsmall.release(); h_done.release();
         h_buf.release(); h_ctl.release(); h_mframes.release(); h_mstatus.release(); h_res.release();
         d_buf.release(); d_ctl.release(); d_qlist.release(); d_tile_cnt.release(); d_seg_off.release();
@@ -200,6 +222,10 @@ struct emurx_ctx {
     // and max_ns: its accumulator rows and flags are zero between calls, cleared like the learning set
     DevBuf<uint8_t> d_nss;
     bool nss_dirty = false;
+    // the answer stages of ingest slots (emurx_ingest_set_answers) share the four scratches above:
+    // each stage waits for the previous one's event and records its own
+    hipEvent_t ans_ev = nullptr;
+    bool ans_recorded = false;
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -591,10 +617,10 @@ bool small_fits(const uint32_t* ctl, uint32_t nmsg, uint32_t n, uint32_t max_til
 
 // the result block of a batch of n descriptor slots and nmsg messages (256-byte aligned parts):
 // allocates both copies and points the views into them
-int set_results(IngestSlot& s, uint32_t n, uint32_t nmsg) {
+int set_results(IngestSlot& s, uint32_t n, uint32_t nmsg, bool answers) {
     // one layout for both copies (and, over no block, for their size)
     auto carve = [&](uint8_t* block, View<emurx_rec>& rec, View<emurx_desc>& desc, View<uint32_t>& q,
-                     View<uint32_t>& stat, View<uint32_t>& qoff, View<uint64_t>& hist) {
+                     View<uint32_t>& stat, View<uint32_t>& qoff, View<uint64_t>& hist, View<uint8_t>* fl) {
         emurx_carver c(block);
         rec.p = c.take<emurx_rec>(n);
         desc.p = c.take<emurx_desc>(n);
@@ -602,19 +628,26 @@ int set_results(IngestSlot& s, uint32_t n, uint32_t nmsg) {
         stat.p = c.take<uint32_t>(nmsg);
         qoff.p = c.take<uint32_t>(EMURX_NUM_QUEUES + 1);
         hist.p = c.take<uint64_t>(2 * EMURX_HIST_BINS);
+        // a batch with answers: the responder's, the learner's and nsstat's per-frame bytes ride the same copy
+        for (int k = 0; k < 3 && answers; ++k) fl[k].p = c.take<uint8_t>(n);
         return c.bytes();
     };
     View<emurx_rec> rec;
     View<emurx_desc> desc;
     View<uint32_t> q, stat, qoff;
     View<uint64_t> hist;
-    const size_t total = carve(nullptr, rec, desc, q, stat, qoff, hist);
+    View<uint8_t> fl[3];
+    const size_t total = carve(nullptr, rec, desc, q, stat, qoff, hist, fl);
     if (s.h_res.alloc(total) || s.d_res.alloc(total)) return EMURX_ENOMEM;
-    carve(s.h_res.p, s.h_rec, s.h_desc, s.h_qlist, s.h_stat, s.h_qoff, s.h_hist);
-    carve(s.d_res.p, s.d_rec, s.d_desc, s.d_packed, s.d_stat, s.d_qoff, s.d_hist_out);
+    carve(s.h_res.p, s.h_rec, s.h_desc, s.h_qlist, s.h_stat, s.h_qoff, s.h_hist, fl);
+    s.h_rspo = fl[0], s.h_lrno = fl[1], s.h_donef = fl[2];
+    carve(s.d_res.p, s.d_rec, s.d_desc, s.d_packed, s.d_stat, s.d_qoff, s.d_hist_out, fl);
+    s.d_rspo = fl[0], s.d_lrno = fl[1], s.d_donef = fl[2];
     s.res_bytes = total;
     return EMURX_OK;
 }
+
+int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n);  // below, with the stages it enqueues
 
 int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nmsg) {
     IngestSlot& s = h->ing[slot];
@@ -645,13 +678,15 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
         if (S > h->cfg.max_frames) return EMURX_ENOSPC;
     }
     base[nmsg] = (uint32_t)S;
+    const uint32_t kinds = s.ans_kinds;
+    if (kinds && end > h->cfg.max_bytes) return EMURX_ENOSPC;  // the answer buffers are sized for max_bytes
     const uint32_t n = (uint32_t)S, nt = ntiles(n);
     const size_t qcap = std::max<size_t>(queue_cap(n), EMURX_QUEUE_TILE);
     const size_t hw = (size_t)EMURX_HIST_SHARDS * 2 * EMURX_HIST_BINS;
     const bool fresh_hist = !s.d_hist.p;
     if (s.d_ctl.alloc((size_t)3 * nmsg + 1) || s.d_qlist.alloc(EMURX_NUM_QUEUES * qcap) ||
         s.d_tile_cnt.alloc((size_t)std::max<uint32_t>(nt, 1) * 16) ||
-        s.d_seg_off.alloc((size_t)std::max<uint32_t>(nt, 1) * 16) || s.d_hist.alloc(hw) || set_results(s, n, nmsg) ||
+        s.d_seg_off.alloc((size_t)std::max<uint32_t>(nt, 1) * 16) || s.d_hist.alloc(hw) || set_results(s, n, nmsg, kinds != 0) ||
         s.h_mframes.alloc(nmsg) || s.h_mstatus.alloc(nmsg))
         return EMURX_ENOMEM;
     hipStream_t st = s.st;
@@ -659,7 +694,8 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     // the pipeline's histogram shards start zeroed (k_qscan leaves them zero)
     if (fresh_hist && !EMURX_HIP_OK(hipMemsetAsync(s.d_hist.p, 0, hw * sizeof(uint64_t), st))) return EMURX_EDEVICE;
     uint32_t trange[EMURX_SMALL_TILES];
-    if (h->ingest_small && small_fits(ctl, nmsg, n, h->small_tiles, trange)) {
+    // (a batch with answers takes the pipeline: the one-launch path leaves no frame in device memory)
+    if (h->ingest_small && !kinds && small_fits(ctl, nmsg, n, h->small_tiles, trange)) {
         // one launch: control words and messages read from the pinned buffers, every result
         // written into the pinned result buffers (no copies)
         if (!s.d_ticket.p) {
@@ -681,6 +717,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
             return EMURX_EDEVICE;
         s.seq = (s.seq + 1) & 0x7fffffffu;  // bit 31 of the completion word: the batch was degraded
         s.small = true;
+        s.ans_batch = 0;
         s.pending = true;
         s.nmsg = nmsg;
         s.slots = n;
@@ -702,11 +739,13 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     if (emurx_launch_queue_pack(s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, n, s.d_seg_off.p, s.d_packed.p,
                                 s.d_qoff.p, s.d_hist.p, s.d_hist_out.p, st))
         return EMURX_EDEVICE;
+    if (kinds && (rc = answer_chain(h, s, n))) return rc;
     // every result in one copy: records, descriptors, packed queues, status, qoff, histogram
     ok = EMURX_HIP_OK(hipMemcpyAsync(s.h_res.p, s.d_res.p, s.res_bytes, D2H, st)) &&
          EMURX_HIP_OK(hipEventRecord(s.done, st));
     if (!ok) return EMURX_EDEVICE;
     s.small = false;
+    s.ans_batch = kinds;
     s.pending = true;
     s.nmsg = nmsg;
     s.slots = n;
@@ -737,6 +776,9 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
     int rc = bind(h);
     if (rc) return rc;
     s.pending = false;
+    s.waited = true;
+    const uint32_t ans = s.ans_batch;
+    s.ans_batch = 0;  // set again below, once the answers are checked and renumbered
     if (!(s.small && h->ingest_spin && spin_done(s.h_done.p, s.seq)) && !EMURX_HIP_OK(hipEventSynchronize(s.done)))
         return EMURX_EDEVICE;
     memset(res, 0, sizeof(*res));
@@ -761,6 +803,8 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
             if (c != base[m] && f) {
                 memmove(s.h_rec.p + c, s.h_rec.p + base[m], (size_t)f * sizeof(emurx_rec));
                 memmove(s.h_desc.p + c, s.h_desc.p + base[m], (size_t)f * sizeof(emurx_desc));
+                for (View<uint8_t>* v : {&s.h_rspo, &s.h_lrno, &s.h_donef})
+                    if (ans) memmove(v->p + c, v->p + base[m], f);
             }
             for (uint32_t k = 0; k < f; ++k) s.remap[base[m] + k] = c + k;
             c += f;
@@ -770,6 +814,27 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
             if (j >= s.slots || s.remap[j] == EMURX_ID_NONE) return EMURX_EDEVICE;
             s.h_qlist.p[i] = s.remap[j];
         }
+    }
+    if (ans) {
+        // the counts k_ans_out copied by are the head's, clamped to the block's capacities: a count
+        // past its capacity (the sizing argument of emurx_ingest_set_answers broken) fails the batch
+        const uint64_t* hd = s.h_ahead.p;
+        const uint64_t nrep = hd[0], nlrn = hd[EMURX_ANS_HEAD_LRN], nns = hd[EMURX_ANS_HEAD_NSS],
+                       ntx = hd[EMURX_ANS_HEAD_TX], txb = hd[EMURX_ANS_HEAD_TX + 1];
+        if (nrep > s.ans_r_cap || ntx > s.ans_r_cap || txb > s.ans_tx_cap || nlrn > s.ans_ev_cap || nns > s.ans_ns_cap)
+            return EMURX_EDEVICE;
+        if (nf < s.slots) {  // slot numbers -> the closed numbering (monotone: ascending `last` survives)
+            auto closed = [&](uint32_t& j) {
+                if (j >= s.slots || s.remap[j] == EMURX_ID_NONE) return false;
+                j = s.remap[j];
+                return true;
+            };
+            for (uint64_t k = 0; k < nrep; ++k)
+                if (!closed(s.h_src.p[k])) return EMURX_EDEVICE;
+            for (uint64_t k = 0; k < nlrn; ++k)
+                if (!closed(s.h_lev.p[k].first) || !closed(s.h_lev.p[k].last)) return EMURX_EDEVICE;
+        }
+        s.ans_batch = ans;
     }
     memcpy(res->qoff, s.h_qoff.p, sizeof(res->qoff));
     if (res->qoff[EMURX_NUM_QUEUES] != nf) return EMURX_EDEVICE;
@@ -911,6 +976,7 @@ void emurx_close(emurx_t* h) {
     h->d_nss.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
+    if (h->ans_ev) (void)hipEventDestroy(h->ans_ev);
     for (auto& e : h->ev)
         if (e) (void)hipEventDestroy(e);
     h->ev.clear();
@@ -1382,6 +1448,41 @@ int emurx_tx_checksum_dev(emurx_t* h, uint8_t* d_frames, const emurx_tx_desc* d_
     return emurx_launch_tx_csum(d_frames, d_desc, n, d_status, st) ? EMURX_EDEVICE : EMURX_OK;
 }
 
+// the framing scratch for n frames: grows on demand behind a synchronisation of `st` (a launch
+// in flight may still read the old one)
+static int txz_reserve(emurx_t* h, uint32_t n, hipStream_t st) {
+    const size_t need = emurx_txz_scratch_bytes(n);
+    if (need > h->d_txz.n) {
+        (void)hipStreamSynchronize(st);
+        if (h->d_txz.alloc(need)) return EMURX_ENOMEM;
+        // the chain's arrival counters (and the feedback words) start at zero (each call's last
+        // arrival resets its own counter)
+        if (!EMURX_HIP_OK(hipMemset(h->d_txz.p, 0, need))) return EMURX_EDEVICE;
+        h->txz_pending = false;
+    }
+    return EMURX_OK;
+}
+
+int emurx_tx_zmq_counted_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n_max,
+                             const uint64_t* d_count, uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off,
+                             uint64_t* d_info, void* stream) {
+    if (!h || !d_msg_off || !d_info || !d_count || (n_max && (!d_frames || !d_desc || (!d_out && out_cap))))
+        return EMURX_EINVAL;
+    if (n_max >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_out & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_count & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = txz_reserve(h, n_max, st))) return rc;
+    // the write's image as the plain calls last chose it; a counted call samples no feedback
+    const int variant = h->txz_mode >= 0 ? h->txz_mode : h->txz_variant;
+    if (emurx_launch_tx_zmq(d_frames, d_desc, n_max, d_out, out_cap, d_msg_off, d_info, h->d_txz.p, st, variant, false,
+                            d_count))
+        return EMURX_EDEVICE;
+    h->last_txz = variant;
+    return EMURX_OK;
+}
+
 int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n,
                      uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off, uint64_t* d_info, void* stream) {
     if (!h || !d_msg_off || !d_info || (n && (!d_frames || !d_desc || (!d_out && out_cap))))
@@ -1390,15 +1491,7 @@ int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
     int rc = bind(h);
     if (rc) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const size_t need = emurx_txz_scratch_bytes(n);
-    if (need > h->d_txz.n) {  // grows on demand; a launch in flight may still read the old one
-        (void)hipStreamSynchronize(st);
-        if (h->d_txz.alloc(need)) return EMURX_ENOMEM;
-        // the chain's arrival counters (and the feedback words) start at zero (each call's last
-        // arrival resets its own counter)
-        if (!EMURX_HIP_OK(hipMemset(h->d_txz.p, 0, need))) return EMURX_EDEVICE;
-        h->txz_pending = false;
-    }
+    if ((rc = txz_reserve(h, n, st))) return rc;
     if (!h->txz_ev && (h->txz_fb.alloc(2) || !EMURX_HIP_OK(hipEventCreateWithFlags(&h->txz_ev, hipEventDisableTiming))))
         return EMURX_ENOMEM;
     if (h->txz_pending && hipEventQuery(h->txz_ev) == hipSuccess) {  // "not ready" is no error
@@ -1575,6 +1668,164 @@ int emurx_route_dev(emurx_t* h, const emurx_rec* d_rec, uint32_t n, uint32_t n_p
                            st, false))
         return EMURX_EDEVICE;
     return route_done(rs, st);
+}
+
+}  // extern "C"
+
+// ---- answers on an ingest slot (emurx_ingest_set_answers / emurx_ingest_answers) -------------
+namespace {
+
+// What a batch of at most max_bytes message bytes can produce.  A frame the responder answers, or
+// the learner folds, has header offsets that fit it (l3 >= 14 and, for ARP, l3 + 28 <= len; the
+// other kinds need more), so it is at least 42 bytes long: at most max_bytes / 42 replies and
+// learn events.  A reply is the frame's own length (ICMP), shorter (ICMPv6), at most 50 bytes (ARP)
+// or at most 94 (ND), so align16(reply) <= max(align16(len), 96) <= len + 54 for len >= 42: the
+// replies take at most max_bytes * 96 / 42 bytes, and their framing 8 bytes per reply more.
+struct AnsCaps {
+    uint64_t rsp, tx;
+    uint32_t r, ev, ns;
+};
+AnsCaps answer_caps(const emurx_t* h) {
+    AnsCaps c;
+    const uint64_t mb = h->cfg.max_bytes;
+    c.r = (uint32_t)std::min<uint64_t>(h->cfg.max_frames, mb / 42 + 1);
+    c.ev = c.r;
+    c.ns = std::min(emurx_nsstat_max_events(h), h->cfg.max_frames);
+    c.rsp = ((mb * 96 / 42 + 96) + 15) & ~(uint64_t)15;
+    c.tx = (c.rsp + 8ull * c.r + 15) & ~(uint64_t)15;
+    return c;
+}
+
+// The answer chain of a batch of n descriptor slots, on the slot's stream behind k_rx and the
+// queue pack: respond, the counted framing of the replies, learn, nsstat (serialised across
+// slots: the four stages' scratch is the handle's), then k_ans_out.  No allocation and no host
+// synchronisation: emurx_ingest_set_answers sized everything.
+int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
+    hipStream_t st = s.st;
+    const uint32_t kinds = s.ans_kinds;
+    uint64_t* rsp_info = s.d_ainfo.p;
+    uint64_t* lrn_info = rsp_info + EMURX_ANS_HEAD_LRN;
+    uint64_t* nss_info = rsp_info + EMURX_ANS_HEAD_NSS;
+    uint64_t* tx_info = rsp_info + EMURX_ANS_HEAD_TX;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
+    if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
+    int rc = respond_kinds(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, EMURX_RSP_INFO_WORDS, s.d_rsp_out.p,
+                           s.ans_rsp_cap, s.d_rsp_desc.p, s.d_rsp_src.p, s.d_rspo.p, rsp_info, st);
+    if (rc) return rc;
+    if ((rc = emurx_tx_zmq_counted_dev(h, s.d_rsp_out.p, s.d_rsp_desc.p, n, rsp_info, s.d_tx.p, s.ans_tx_cap,
+                                       s.d_tx_off.p, tx_info, st)))
+        return rc;
+    const uint32_t lk = ((kinds & EMURX_RSPK_ARP) ? EMURX_LRNK_ARP : 0u) | ((kinds & EMURX_RSPK_ND) ? EMURX_LRNK_ND : 0u);
+    if (lk) {
+        rc = emurx_learn_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, lk, s.d_lev.p, emurx_learn_max_events(h),
+                             s.d_lrno.p, lrn_info, st);
+    } else {  // nothing to learn from: every outcome EMURX_LRN_NONE, no event
+        rc = EMURX_HIP_OK(hipMemsetAsync(lrn_info, 0, EMURX_LRN_INFO_WORDS * sizeof(uint64_t), st)) &&
+                     (!n || EMURX_HIP_OK(hipMemsetAsync(s.d_lrno.p, 0, n, st)))
+                 ? EMURX_OK
+                 : EMURX_EDEVICE;
+    }
+    if (rc) return rc;
+    if ((rc = emurx_nsstat_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, s.d_rspo.p, s.d_lrno.p, s.d_nsev.p,
+                               emurx_nsstat_max_events(h), s.d_donef.p, nss_info, st)))
+        return rc;
+    // the shared scratch is free again: the next slot's stage may start while this one copies out
+    if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
+    h->ans_recorded = true;
+    const emurx_ans_out a{reinterpret_cast<const unsigned long long*>(rsp_info),
+                          reinterpret_cast<const unsigned long long*>(tx_info),
+                          reinterpret_cast<const unsigned long long*>(lrn_info),
+                          reinterpret_cast<const unsigned long long*>(nss_info),
+                          s.d_tx.p,
+                          reinterpret_cast<const unsigned long long*>(s.d_tx_off.p),
+                          s.d_rsp_src.p,
+                          s.d_lev.p,
+                          s.d_nsev.p,
+                          reinterpret_cast<uint8_t*>(s.h_ahead.p),
+                          s.h_tx.p,
+                          reinterpret_cast<uint8_t*>(s.h_tx_off.p),
+                          reinterpret_cast<uint8_t*>(s.h_src.p),
+                          reinterpret_cast<uint8_t*>(s.h_lev.p),
+                          reinterpret_cast<uint8_t*>(s.h_nsev.p),
+                          s.ans_tx_cap,
+                          s.ans_r_cap,
+                          s.ans_ev_cap,
+                          s.ans_ns_cap};
+    return emurx_launch_ans_out(a, n, st) ? EMURX_EDEVICE : EMURX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds) {
+    if (!h || slot >= EMURX_INGEST_SLOTS || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    IngestSlot& s = h->ing[slot];
+    if (s.pending) return EMURX_EINVAL;
+    if (!kinds || s.h_ans.p) {  // off, or sized by an earlier call
+        s.ans_kinds = kinds;
+        return EMURX_OK;
+    }
+    // everything the chain needs, now: no submit allocates or synchronises for it.  The shared
+    // scratches may be in use by launches in flight, so the device is idle before they grow.
+    if (!EMURX_HIP_OK(hipDeviceSynchronize())) return EMURX_EDEVICE;
+    const uint32_t mf = std::min<uint32_t>(h->cfg.max_frames, EMURX_TX_ZMQ_MAX_FRAMES - 1);
+    if (!h->ans_ev && !EMURX_HIP_OK(hipEventCreateWithFlags(&h->ans_ev, hipEventDisableTiming))) return EMURX_EDEVICE;
+    if ((rc = txz_reserve(h, mf, h->stream))) return rc;
+    if (emurx_rsp_scratch_bytes(mf) > h->d_rsp.n && h->d_rsp.alloc(emurx_rsp_scratch_bytes(mf))) return EMURX_ENOMEM;
+    const AnsCaps c = answer_caps(h);
+    // device arrays: a descriptor, a source index and a message offset per descriptor slot (the
+    // stages' own capacities), the events at the stages' ev_cap; two elements of slack each, so
+    // that k_ans_out's last 16-byte vector of any count is readable
+    if (s.d_rsp_out.alloc(c.rsp + 16) || s.d_tx.alloc(c.tx + 16) || s.d_rsp_desc.alloc((size_t)mf + 2) ||
+        s.d_rsp_src.alloc((size_t)mf + 4) || s.d_tx_off.alloc((size_t)mf + 3) || s.d_ainfo.alloc(EMURX_ANS_HEAD_WORDS) ||
+        s.d_lev.alloc((size_t)emurx_learn_max_events(h) + 2) || s.d_nsev.alloc((size_t)emurx_nsstat_max_events(h) + 2))
+        return EMURX_ENOMEM;
+    if (!EMURX_HIP_OK(hipMemset(s.d_ainfo.p, 0, EMURX_ANS_HEAD_WORDS * sizeof(uint64_t)))) return EMURX_EDEVICE;
+    auto carve = [&](uint8_t* block) {
+        emurx_carver k(block);
+        s.h_ahead.p = k.take<uint64_t>(EMURX_ANS_HEAD_WORDS);
+        s.h_tx_off.p = k.take<uint64_t>((size_t)c.r + 1);
+        s.h_src.p = k.take<uint32_t>(c.r);
+        s.h_lev.p = k.take<emurx_learn_ev>(c.ev);
+        s.h_nsev.p = k.take<emurx_nsstat_ev>(c.ns);
+        s.h_tx.p = k.take<uint8_t>(c.tx);
+        return k.bytes();
+    };
+    if (s.h_ans.alloc(carve(nullptr))) return EMURX_ENOMEM;
+    carve(s.h_ans.p);
+    memset(s.h_ahead.p, 0, EMURX_ANS_HEAD_WORDS * sizeof(uint64_t));
+    s.ans_rsp_cap = c.rsp, s.ans_tx_cap = c.tx, s.ans_r_cap = c.r, s.ans_ev_cap = c.ev, s.ans_ns_cap = c.ns;
+    s.ans_kinds = kinds;
+    return EMURX_OK;
+}
+
+int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out) {
+    if (!h || !out || slot >= EMURX_INGEST_SLOTS) return EMURX_EINVAL;
+    const IngestSlot& s = h->ing[slot];
+    if (s.pending || !s.waited) return EMURX_EINVAL;
+    if (!s.ans_batch) return EMURX_ENOENT;
+    const uint64_t* hd = s.h_ahead.p;
+    memset(out, 0, sizeof(*out));
+    out->tx = s.h_tx.p;
+    out->tx_msg_off = s.h_tx_off.p;
+    out->n_tx_msgs = (uint32_t)hd[EMURX_ANS_HEAD_TX];
+    out->n_replies = (uint32_t)hd[0];
+    out->tx_bytes = hd[EMURX_ANS_HEAD_TX + 1];
+    out->reply_src = s.h_src.p;
+    out->rsp_outcome = s.h_rspo.p;
+    out->lrn_outcome = s.h_lrno.p;
+    out->done = s.h_donef.p;
+    out->learn_ev = s.h_lev.p;
+    out->n_learn = (uint32_t)hd[EMURX_ANS_HEAD_LRN];
+    out->ns_ev = s.h_nsev.p;
+    out->n_ns = (uint32_t)hd[EMURX_ANS_HEAD_NSS];
+    memcpy(out->rsp_info, hd, sizeof(out->rsp_info));
+    memcpy(out->lrn_info, hd + EMURX_ANS_HEAD_LRN, sizeof(out->lrn_info));
+    memcpy(out->nss_info, hd + EMURX_ANS_HEAD_NSS, sizeof(out->nss_info));
+    return EMURX_OK;
 }
 
 }  // extern "C"

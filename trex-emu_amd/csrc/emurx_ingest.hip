@@ -13,6 +13,8 @@
 //               per-tile queue output in the packed queue-major order, qoff[14], and the
 //               histogram shards folded into one copy (shards left zero for the next batch)
 //   k_qpack     one workgroup per tile: copies its segments to their packed positions
+//   k_ans_out   (a slot with answers on) behind the answer chain: what respond, the tx framing,
+//               learn and nsstat produced, by their device-side counts, into pinned host memory
 // Messages are independent, so the walk needs no cross-lane communication; it is a chain of
 // dependent loads per message, latency bound and far off the HBM roofline (the host batch
 // is PCIe bound).
@@ -690,7 +692,57 @@ __global__ __launch_bounds__(kBlock) void k_ingest_small(const SmallArgs a) {
     SSTAMP(9);
 }
 
+// ---- a slot's answers (emurx_ingest_set_answers): the variable-size outputs to the host --------
+// One launch behind the answer chain (respond, counted tx framing, learn, nsstat) on the slot's
+// stream.  The counts are known only on the device, in the stages' info words; every workgroup
+// reads them and the grid copies, with 16-byte stores over the bus into the slot's pinned answer
+// block (as k_ingest_small writes its results), exactly what was produced: the four info blocks
+// (the block's head), tx_msg_off[n_msgs + 1], reply_src[replies], the learn events, the Namespace
+// events and the framed tx bytes.  A batch with no reply and no event moves the head alone.
+// Every count is clamped to its region's capacity (the host checks the head's counts against the
+// same capacities and fails the batch instead of reading a truncated region).
+__global__ __launch_bounds__(kBlock) void k_ans_out(const emurx_ans_out a) {
+    const uint64_t nrep = min((uint64_t)a.rsp_info[0], (uint64_t)a.r_cap);
+    const uint64_t nmsg = min((uint64_t)a.tx_info[0], (uint64_t)a.r_cap);
+    const uint64_t txb = min((uint64_t)a.tx_info[1], a.tx_cap);
+    const uint64_t nlrn = min((uint64_t)a.lrn_info[0], (uint64_t)a.ev_cap);
+    const uint64_t nns = min((uint64_t)a.nss_info[0], (uint64_t)a.ns_cap);
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x, gsz = (uint64_t)gridDim.x * kBlock;
+    // the regions start on 256-byte boundaries on both sides and their capacities are whole
+    // 16-byte vectors, so a count's last vector stays inside its region
+    auto copy = [&](const void* src, void* dst, uint64_t bytes) {
+        const uint64_t nv = (bytes + 15) >> 4;
+        for (uint64_t v = gid; v < nv; v += gsz)
+            reinterpret_cast<uint4*>(dst)[v] = gld16(reinterpret_cast<const uint4*>(src) + v);
+    };
+    if (blockIdx.x == 0 && threadIdx.x < EMURX_ANS_HEAD_WORDS / 2) {  // the head: two info words per lane
+        auto word = [&](uint32_t i) -> unsigned long long {
+            return i < EMURX_ANS_HEAD_LRN   ? a.rsp_info[i]
+                   : i < EMURX_ANS_HEAD_NSS ? a.lrn_info[i - EMURX_ANS_HEAD_LRN]
+                   : i < EMURX_ANS_HEAD_TX  ? a.nss_info[i - EMURX_ANS_HEAD_NSS]
+                   : i < EMURX_ANS_HEAD_TX + 2 ? a.tx_info[i - EMURX_ANS_HEAD_TX]
+                                               : 0ull;
+        };
+        const unsigned long long w0 = word(2 * threadIdx.x), w1 = word(2 * threadIdx.x + 1);
+        reinterpret_cast<uint4*>(a.h_head)[threadIdx.x] =
+            make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
+    }
+    copy(a.tx_off, a.h_tx_off, (nmsg + 1) * 8);
+    copy(a.src, a.h_src, nrep * 4);
+    copy(a.lev, a.h_lev, nlrn * sizeof(emurx_learn_ev));
+    copy(a.nsev, a.h_nsev, nns * sizeof(emurx_nsstat_ev));
+    copy(a.tx, a.h_tx, txb);
+}
+
 }  // namespace emurx
+
+int emurx_launch_ans_out(const emurx_ans_out& a, uint32_t n, hipStream_t st) {
+    using namespace emurx;
+    // a workgroup per tile of the batch, at most 256: the volume is bounded by the batch's size,
+    // and a workgroup with nothing to copy ends after reading the five counts
+    const uint32_t g = std::min<uint32_t>(std::max<uint32_t>((n + kBlock - 1) / kBlock, 1), 256);
+    return EMURX_HIP_OK(emurx_launch(k_ans_out, dim3(g), dim3(kBlock), 0, st, a)) ? 0 : -1;
+}
 
 int emurx_launch_zmq_walk(const uint8_t* buf, const uint32_t* ctl, uint32_t nmsg, emurx_desc* desc,
                           uint32_t* msg_stat, hipStream_t st, bool keys) {

@@ -167,6 +167,27 @@ int emurx_launch_queue_pack(const uint32_t* qlist, uint32_t qcap, const uint32_t
                             uint32_t* seg_off, uint32_t* packed, uint32_t* qoff, uint64_t* hist,
                             uint64_t* hist_out, hipStream_t st);
 
+// A slot's answers to the host (k_ans_out, emurx_ingest.hip): the stages' info words (device) give
+// the counts; the device outputs are copied into the regions of the slot's pinned answer block,
+// whose head is EMURX_ANS_HEAD_WORDS u64: rsp_info, lrn_info, nss_info, the framing's {n_msgs,
+// total}, zeros.  Capacities: r_cap replies (and r_cap + 1 offsets), tx_cap bytes, ev_cap learn
+// events, ns_cap Namespace events; every device array readable to the next 16-byte boundary past
+// its capacity.  n: the batch's descriptor slots (sizes the grid).  One launch.
+enum { EMURX_ANS_HEAD_LRN = EMURX_RSP_INFO_WORDS, EMURX_ANS_HEAD_NSS = EMURX_ANS_HEAD_LRN + EMURX_LRN_INFO_WORDS,
+       EMURX_ANS_HEAD_TX = EMURX_ANS_HEAD_NSS + EMURX_NSS_INFO_WORDS, EMURX_ANS_HEAD_WORDS = EMURX_ANS_HEAD_TX + 4 };
+struct emurx_ans_out {
+    const unsigned long long *rsp_info, *tx_info, *lrn_info, *nss_info;
+    const uint8_t* tx;
+    const unsigned long long* tx_off;
+    const uint32_t* src;
+    const emurx_learn_ev* lev;
+    const emurx_nsstat_ev* nsev;
+    uint8_t *h_head, *h_tx, *h_tx_off, *h_src, *h_lev, *h_nsev;  // pinned host
+    uint64_t tx_cap;
+    uint32_t r_cap, ev_cap, ns_cap;
+};
+int emurx_launch_ans_out(const emurx_ans_out& a, uint32_t n, hipStream_t st);
+
 // The handle internals the communicator (emurx_comm.cpp) uses; defined in emurx_api.cpp.
 struct emurx_comm_state;
 int emurx_handle_bind(emurx_t* h);           // make the handle's device current (EMURX_OK / error)
@@ -215,4 +236,6 @@ enum { EMURX_TXZ_WIDE = 0, EMURX_TXZ_NARROW = 1, EMURX_TXZ_LONG = 2 };
 constexpr uint32_t emurx_txz_img_narrow_rows = 4608 / 16, emurx_txz_img_wide_rows = 6144 / 16;
 int emurx_launch_tx_zmq(const uint8_t* frames, const emurx_desc* desc, uint32_t n, uint8_t* out, uint64_t cap,
                         uint64_t* msg_off, uint64_t* info, void* scratch, hipStream_t st, int variant = EMURX_TXZ_WIDE,
-                        bool feedback = false);
+                        bool feedback = false, const uint64_t* count = nullptr);
+// count (device memory, nullable): the call frames min(*count, n) descriptors, read when the
+// kernels run; grids, tables and scratch are laid out for n (emurx_tx_zmq_counted_dev)

@@ -72,7 +72,8 @@ constexpr uint32_t kTxUnitWaves = 16;  // a level-1 unit (64 tiles, 4096 frames)
 constexpr uint32_t kTxTilesPerWave = 64 / kTxUnitWaves;
 constexpr uint32_t kTxBlocks = 8, kTxBlock = 64 / kTxBlocks;  // compose: 8 blocks of 8 children
 struct TxChain {
-    uint32_t L, n, ntiles;
+    uint32_t L, n, ntiles;                   // n: the frames the grids, levels and tables are laid out for
+    const unsigned long long* count;         // non-null: the frames of this call, min(*count, n), read by the kernels
     uint32_t units[kTxMaxLevels];
     uint32_t* T[kTxMaxLevels];               // [units][64]; level 0 unused (tables stay in LDS)
     unsigned long long* B[kTxMaxLevels];     // [units] frame bytes; level 0 unused
@@ -82,6 +83,14 @@ struct TxChain {
     unsigned long long *msg_off, *info;
     uint32_t* fb;  // non-null: the largest bound of a tile's output rows and ~ the smallest, atomicMax
 };
+// The frames of this call.  A counted call (emurx_tx_zmq_counted_dev) lays everything out for
+// c.n = n_max and frames the first min(*count, n_max): a tile at or past the count loads no
+// descriptor, has lim 0 and zero bytes, so its table takes every entry to exit 0 with no message
+// started -- the state the chain leaves the last frame's tile in -- and it composes as an empty
+// tile; its workgroup still makes every arrival of the n_max-sized grid.
+__device__ __forceinline__ uint32_t tx_frames(const TxChain& c) {
+    return c.count ? (uint32_t)min(*c.count, (unsigned long long)c.n) : c.n;
+}
 struct TxChainLds {
     uint32_t t[64][64];         // the children's tables
     unsigned long long b[64];   // the children's bytes
@@ -152,7 +161,7 @@ __device__ void tx_compose_table(const TxChain& c, uint32_t k, uint32_t p, uint3
     }
     tx_block_sync();
 }
-__device__ void tx_compose_rows(const TxChain& c, uint32_t k, uint32_t p, uint32_t cn, TxChainLds& S) {
+__device__ void tx_compose_rows(const TxChain& c, uint32_t n, uint32_t k, uint32_t p, uint32_t cn, TxChainLds& S) {
     const uint32_t wv = threadIdx.x / kWave, lane = lane_id();
     if (wv < kTxBlocks) {  // R[ch][e] = the block's running state from the block's entry
         const uint32_t pe = S.u.up.p[wv][lane], x0 = pe & 63u, m0 = pe >> 6;
@@ -167,7 +176,7 @@ __device__ void tx_compose_rows(const TxChain& c, uint32_t k, uint32_t p, uint32
         const uint32_t r = S.u.up.p[kTxBlocks][0];
         unsigned long long tot = 0;
         for (uint32_t i = 0; i < cn; ++i) tot += S.b[i];
-        const unsigned long long nm = r >> 6, total = 4ull * nm + 4ull * c.n + tot;
+        const unsigned long long nm = r >> 6, total = 4ull * nm + 4ull * n + tot;
         c.info[0] = nm;
         c.info[1] = total;
         c.msg_off[nm] = total;
@@ -181,7 +190,7 @@ __device__ void tx_compose_rows(const TxChain& c, uint32_t k, uint32_t p, uint32
 __global__ __launch_bounds__(kTxUnitWaves * kWave) void k_txz_chain(const emurx_desc* __restrict__ d, const TxChain c) {
     __shared__ TxChainLds S;
     const uint32_t wv = threadIdx.x / kWave, lane = lane_id();
-    const uint32_t p = blockIdx.x, n = c.n;
+    const uint32_t p = blockIdx.x, n = tx_frames(c);
     const uint32_t t0 = p * 64 + wv * kTxTilesPerWave;  // this wave's first tile
     const uint32_t wbase = t0 * kTxTile;
     // ---- leaf: lens of 5 rows (4 tiles + the next one), all loads issued before use
@@ -288,7 +297,7 @@ __global__ __launch_bounds__(kTxUnitWaves * kWave) void k_txz_chain(const emurx_
                 if (S.last) tx_st_agent(&c.cnt[k + 1][par], 0u);  // all arrived: ready for the next call
             }
         }
-        tx_compose_rows(c, k, up, cn, S);
+        tx_compose_rows(c, n, k, up, cn, S);
         if (top) return;
         tx_block_sync();      // S.last, and the rows are done with the LDS the parent's compose reuses
         if (!S.last) return;  // workgroup-uniform
@@ -343,7 +352,7 @@ __device__ __forceinline__ void lds_or4(uint32_t* o32, uint32_t p, uint32_t v) {
 constexpr uint32_t kTxImgWide = 6144, kTxImgNarrow = 4608, kTxLongLds = 6 * kWave * 4 + 512 * 4;
 template <uint32_t kTxImg>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == kTxImgWide ? 6 : 8))) void k_txz_emit(const uint8_t* __restrict__ frames, const emurx_desc* __restrict__ d,
-                                                  uint32_t n, uint32_t ntiles, const TxChain c,
+                                                  uint32_t ntiles, const TxChain c,
                                                   uint8_t* __restrict__ out, unsigned long long cap,
                                                   unsigned long long* __restrict__ msg_off) {
     constexpr uint32_t kLds = kTxImg > kTxLongLds ? kTxImg : kTxLongLds;
@@ -355,8 +364,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTxImg == k
     // config E (1M IMIX frames): 1 wave 263 us per call, 2 waves 262-268, 4 waves 288 (DESIGN.md
     // §6 round 6): the launch's tail is not what E's write pays for.
     const uint32_t t = blockIdx.x * 4 + wv;
-    if (t >= ntiles) return;  // wave-uniform
-    const uint32_t base = t * kTxTile;
+    const uint32_t base = t * kTxTile, n = tx_frames(c);
+    // wave-uniform; a tile at or past a counted call's frames writes nothing (and n - base below,
+    // here and in tx_endrel_v, never wraps)
+    if (t >= ntiles || base >= n) return;
     // loads that wait on nothing first: this and the next tile's descriptors, the tile base
     const uint32_t lim = min(n - base, kTxTile);
     const bool valid = lane < lim;
@@ -581,7 +592,8 @@ size_t emurx_txz_scratch_bytes(uint32_t n) {
 }
 
 int emurx_launch_tx_zmq(const uint8_t* frames, const emurx_desc* desc, uint32_t n, uint8_t* out, uint64_t cap,
-                        uint64_t* msg_off, uint64_t* info, void* scratch, hipStream_t st, int variant, bool feedback) {
+                        uint64_t* msg_off, uint64_t* info, void* scratch, hipStream_t st, int variant, bool feedback,
+                        const uint64_t* count) {
     using namespace emurx;
     unsigned long long* mo = reinterpret_cast<unsigned long long*>(msg_off);
     unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
@@ -590,6 +602,7 @@ int emurx_launch_tx_zmq(const uint8_t* frames, const emurx_desc* desc, uint32_t 
         return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 16, st)) && EMURX_HIP_OK(hipMemsetAsync(mo, 0, 8, st)) ? 0 : -1;
     TxChain c{};
     c.n = n;
+    c.count = reinterpret_cast<const unsigned long long*>(count);
     c.ntiles = (n + 63) / 64;
     c.units[0] = c.ntiles;
     c.msg_off = mo;
@@ -618,7 +631,7 @@ int emurx_launch_tx_zmq(const uint8_t* frames, const emurx_desc* desc, uint32_t 
         e = emurx_launch(variant == EMURX_TXZ_NARROW ? k_txz_emit<kTxImgNarrow>
                          : variant == EMURX_TXZ_LONG ? k_txz_emit<0>
                                                      : k_txz_emit<kTxImgWide>,
-                         dim3((nt + 3) / 4), dim3(256), 0, st, frames, desc, n, nt, c, out, (unsigned long long)cap, mo);
+                         dim3((nt + 3) / 4), dim3(256), 0, st, frames, desc, nt, c, out, (unsigned long long)cap, mo);
     }
     return EMURX_HIP_OK(e) ? 0 : -1;
 }

@@ -183,6 +183,15 @@ class IngestResult(C.Structure):
                 ("one_launch", C.c_uint32), ("degraded", C.c_uint32)]
 
 
+class Answers(C.Structure):
+    """emurx_answers: a slot's device answers (emurx_ingest_answers); pointers into library memory."""
+    _fields_ = [("tx", C.c_void_p), ("tx_msg_off", C.c_void_p), ("n_tx_msgs", C.c_uint32), ("n_replies", C.c_uint32),
+                ("tx_bytes", C.c_uint64), ("reply_src", C.c_void_p), ("rsp_outcome", C.c_void_p),
+                ("lrn_outcome", C.c_void_p), ("done", C.c_void_p), ("learn_ev", C.c_void_p), ("n_learn", C.c_uint32),
+                ("ns_ev", C.c_void_p), ("n_ns", C.c_uint32), ("rsp_info", C.c_uint64 * RSP_INFO_WORDS),
+                ("lrn_info", C.c_uint64 * LRN_INFO_WORDS), ("nss_info", C.c_uint64 * NSS_INFO_WORDS)]
+
+
 class DevOut(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("qlist", C.c_void_p), ("qcap", C.c_uint32),
                 ("tile_cnt", C.c_void_p), ("hist", C.c_void_p), ("flow", C.c_void_p)]
@@ -257,8 +266,11 @@ SIGNATURES = [
     ("emurx_ingest_submit", C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     ("emurx_ingest_wait", C.c_int, [_P, C.c_uint32, C.POINTER(IngestResult)]),
     ("emurx_ingest_stream", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("emurx_ingest_set_answers", C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    ("emurx_ingest_answers", C.c_int, [_P, C.c_uint32, C.POINTER(Answers)]),
     ("emurx_tx_checksum_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
+    ("emurx_tx_zmq_counted_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_learn_max_events", C.c_uint32, [_P]),

@@ -259,6 +259,31 @@ class RxPath:
                     msg_frames=view(r.msg_frames, m, np.uint32), msg_status=view(r.msg_status, m, np.uint8),
                     counters=r.delta.as_dict(), n=n, one_launch=bool(r.one_launch), degraded=bool(r.degraded))
 
+    def ingest_set_answers(self, slot: int, kinds: int) -> None:
+        """Run the device answer chain (respond, tx framing, learn, nsstat) on the slot's later
+        batches: kinds abi.RSPK_* bits, 0 turns it off (include/emu_rx.h emurx_ingest_set_answers)."""
+        abi.check(self.lib.emurx_ingest_set_answers(self.h, slot, kinds), "ingest_set_answers")
+
+    def ingest_answers(self, slot: int, n_frames: int) -> dict:
+        """The answers of the slot's batch, after its ingest_wait (n_frames: that result's n), as
+        numpy copies: tx (the framed replies), tx_msg_off, reply_src, rsp_outcome, lrn_outcome,
+        done, learn_ev, ns_ev, rsp_info, lrn_info, nss_info, n_replies, n_tx_msgs, tx_bytes."""
+        a = abi.Answers()
+        abi.check(self.lib.emurx_ingest_answers(self.h, slot, C.byref(a)), "ingest_answers")
+
+        def copy(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            b = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dt).itemsize,))
+            return b.view(dt).copy()
+        return dict(tx=copy(a.tx, int(a.tx_bytes), np.uint8), tx_msg_off=copy(a.tx_msg_off, a.n_tx_msgs + 1, np.uint64),
+                    reply_src=copy(a.reply_src, a.n_replies, np.uint32), rsp_outcome=copy(a.rsp_outcome, n_frames, np.uint8),
+                    lrn_outcome=copy(a.lrn_outcome, n_frames, np.uint8), done=copy(a.done, n_frames, np.uint8),
+                    learn_ev=copy(a.learn_ev, a.n_learn, abi.LEARN_EV_DTYPE), ns_ev=copy(a.ns_ev, a.n_ns, abi.NSSTAT_EV_DTYPE),
+                    rsp_info=np.array(a.rsp_info, np.uint64), lrn_info=np.array(a.lrn_info, np.uint64),
+                    nss_info=np.array(a.nss_info, np.uint64), n_replies=int(a.n_replies), n_tx_msgs=int(a.n_tx_msgs),
+                    tx_bytes=int(a.tx_bytes))
+
     # ---- tx-side checksum generation ------------------------------------------------------
     def tx_checksum_dev(self, frames, desc, n: int, status=None, stream=None):
         """Rewrite the checksums selected by each TX_DESC_DTYPE descriptor, in place on the
@@ -272,6 +297,14 @@ class RxPath:
         [n + 1], info u64 {n_msgs, total bytes}."""
         return abi.check(self.lib.emurx_tx_zmq_dev(self.h, _addr(frames), _addr(desc), n, _addr(out), cap,
                                                    _addr(msg_off), _addr(info), _stream(stream)), "tx_zmq_dev")
+
+    def tx_zmq_counted_dev(self, frames, desc, n_max: int, count, out, cap: int, msg_off, info, stream=None):
+        """tx_zmq_dev over the first min(count[0], n_max) descriptors, `count` a u64 in device
+        memory read when the kernels run (include/emu_rx.h emurx_tx_zmq_counted_dev): the
+        responder's info is the intended count.  msg_off u64 [n_max + 1]."""
+        return abi.check(self.lib.emurx_tx_zmq_counted_dev(self.h, _addr(frames), _addr(desc), n_max, _addr(count),
+                                                           _addr(out), cap, _addr(msg_off), _addr(info),
+                                                           _stream(stream)), "tx_zmq_counted_dev")
 
     def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None,
                     kinds=None):
