@@ -644,9 +644,11 @@ enum emurx_rsp {            /* per-frame outcome, d_outcome[i] */
     EMURX_RSP_NONE = 0,       /* not a frame this call answers */
     EMURX_RSP_ARP = 1, EMURX_RSP_ICMP = 2, EMURX_RSP_ICMPV6 = 3,   /* reply written */
     EMURX_RSP_DROP_MCAST = 4, /* the handler counts pktRxErrMulticastB and sends nothing */
-    EMURX_RSP_HOST = 5,       /* the Go handler must answer (timestamp request; client not in this handle's tables) */
+    EMURX_RSP_HOST = 5,       /* the Go handler must answer (a timestamp request without EMURX_RSPK_TS; client not in this handle's tables) */
     EMURX_RSP_NOSPC = 6,      /* a reply was due but did not fit out_cap */
-    EMURX_RSP_ND = 7          /* reply written (neighbour advertisement; emurx_respond_kinds_dev only) */
+    EMURX_RSP_ND = 7,         /* reply written (neighbour advertisement; emurx_respond_kinds_dev only) */
+    EMURX_RSP_TS = 8,         /* timestamp reply written (emurx_respond_ts_dev with EMURX_RSPK_TS only) */
+    EMURX_RSP_DROP_SHORT = 9  /* len - l4 < 20: the handler counts pktRxErrTooShort, sends nothing (EMURX_RSPK_TS only) */
 };
 int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
                       const emurx_rec* d_rec, uint32_t n,
@@ -703,6 +705,44 @@ int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_des
                             const emurx_rec* d_rec, uint32_t n, uint32_t kinds,
                             uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
                             uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
+/* The same call with a fifth answer, the one whose only outside input is the time of day:
+     ICMPv4 timestamp reply to a timestamp request
+                      plugins/icmp/icmp.go:396-462 -> PluginIcmpNs.HandleEcho(ps, true) :289-325
+   kinds: EMURX_RSPK_* bits in 1..EMURX_RSPK_ALL_TS (0 or a bit above is EMURX_EINVAL).  With
+   kinds <= EMURX_RSPK_ALL the call is emurx_respond_kinds_dev(kinds) byte for byte (the same
+   kernels; ip_time_ms is not read).  ip_time_ms: what the reference's iptime() (icmp.go:281-287)
+   returns, milliseconds since midnight UTC; it is written as given, any u32, no range check.  The
+   handler reads the clock per frame; this call has one value per batch.  d_info
+   is u64[EMURX_RSP_INFO_WORDS] = {replies written (timestamp replies included), bytes needed,
+   frames with outcome 1..9, zeros}.  Everything else is emurx_respond_kinds_dev's contract:
+   capacity, the NOSPC prefix rule, alignment, three launches, no host synchronisation, the
+   handle's shared scratch.
+     icmp    a candidate if kinds has EMURX_RSPK_ICMP or EMURX_RSPK_TS (status OK, lookup
+             EMURX_LK_CLIENT, callback icmp, no hole: the client lookup and IsUnicastToMe of
+             icmp.go:417-427 are the classifier's).  In this order: header offsets that do not fit
+             (l3 < 14, l3 + 20 > len, l4 + 8 > len) -> HOST; the source-IP rule (:429-436) ->
+             DROP_MCAST, for every type; type, code (8, 0) -> the echo rule above if kinds has
+             EMURX_RSPK_ICMP, else NONE; (13, 0) without EMURX_RSPK_TS -> HOST; any other -> NONE.
+     ts      (13, 0) with EMURX_RSPK_TS, HandleEcho(ps, true) in the handler's order: the Ethernet
+             source p[6] has the group bit (the swapped destination is broadcast or multicast,
+             :293-299) -> DROP_MCAST; len - l4 < 20 (:312-316, behind the multicast test) ->
+             EMURX_RSP_DROP_SHORT; an odd l4 (no parse of ours produces one) -> HOST; else
+             EMURX_RSP_TS.  The reply is the whole frame (tags and trailing bytes kept, :324) with
+             the Ethernet addresses swapped (:293-294), the IPv4 addresses swapped (:301-302; the
+             header checksum holds), p[l4], p[l4+1] = 14, 0 (:310-311), ip_time_ms big-endian in
+             p[l4+12:l4+16] and again in p[l4+16:l4+20] (receive and transmit, :317-319; the
+             originate timestamp p[l4+8:l4+12] stays) and the ICMP checksum recomputed (:320,
+             UpdateChecksum, gopacket layers/icmp4.go:252-256: p[l4+2:l4+4] zeroed, then
+             tcpipChecksum(p[l4:len], 0), layers/tcpip.go:76-94): the sum of the big-endian byte
+             pairs, an odd last byte as its high byte, folded while above 0xffff, complemented.
+             The span is the rest of the frame and not the IPv4 total length: Ethernet padding
+             and trailers are summed; a folded sum of 0xffff stores 0x0000. */
+#define EMURX_RSPK_TS 16u           /* ICMPv4 timestamp request -> timestamp reply */
+#define EMURX_RSPK_ALL_TS 31u
+int emurx_respond_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                         const emurx_rec* d_rec, uint32_t n, uint32_t kinds, uint32_t ip_time_ms,
+                         uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
+                         uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream);
 
 /* ---- ARP and ND cache learning, folded per batch ------------------------------------------
    The ARP handler learns the sender of every request before it answers and of every unicast
@@ -884,7 +924,9 @@ enum emurx_nsc {                 /* index into emurx_nsstat_ev.cnt */
     EMURX_NSC_ND_TX_ADV_UNICAST = 15,   /* pktTxNeighborAdvUnicast             */
     EMURX_NSC_ND_TX_DAD_ERROR = 16,     /* pktTxNeighborDADError               */
     EMURX_NSC_ND_RX_NA = 17,            /* pktRxNeighborAdvertisement          */
-    EMURX_NSC_ND_RX_NA_LEARN = 18       /* pktRxNeighborAdvLearn; 19..21 zero  */
+    EMURX_NSC_ND_RX_NA_LEARN = 18,      /* pktRxNeighborAdvLearn               */
+    /* 19, counted by emurx_nsstat_ts_dev alone: IcmpNsStats.pktRxErrTooShort; 20..21 zero */
+    EMURX_NSC_ICMP_ERR_TOO_SHORT = EMURX_NSC_ND_RX_NA_LEARN + 1
 };
 #define EMURX_NSC_WORDS 22
 #define EMURX_NSS_INFO_WORDS 8
@@ -899,6 +941,22 @@ int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
                      const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome,
                      emurx_nsstat_ev* d_ev, uint32_t ev_cap,
                      uint8_t* d_done, uint64_t* d_info, void* stream);
+/* The same call for outcomes of emurx_respond_ts_dev.  kinds in 1..EMURX_RSPK_ALL_TS; EMURX_RSPK_TS
+   without EMURX_RSPK_ICMP is EMURX_EINVAL (the timestamp rule refines the icmp handler's).  With
+   kinds <= EMURX_RSPK_ALL it is emurx_nsstat_dev(kinds).  d_rsp_outcome: the outcome array of an
+   emurx_respond_ts_dev call on the same batch and records with at least these kinds.  With
+   EMURX_RSPK_TS, an icmp frame with lookup CLIENT and responder outcome
+     EMURX_RSP_TS          counts pktRxIcmpQuery and pktTxIcmpResponse (icmp.go:322-323; the one
+                           word EMURX_NSC_ICMP_ECHO), done 1;
+     EMURX_RSP_DROP_SHORT  counts pktRxErrTooShort (icmp.go:313; EMURX_NSC_ICMP_ERR_TOO_SHORT, a
+                           counter a frame bumps alone: it adds to the event's `frames`), done 1;
+   a timestamp request with DROP_MCAST counts pktRxErrMulticastB like every DROP_MCAST, done 1;
+   with HOST, NOSPC or NONE it stays at done 0.  Everything else is emurx_nsstat_dev's contract. */
+int emurx_nsstat_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                        const emurx_rec* d_rec, uint32_t n, uint32_t kinds,
+                        const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome,
+                        emurx_nsstat_ev* d_ev, uint32_t ev_cap,
+                        uint8_t* d_done, uint64_t* d_info, void* stream);
 
 /* ---- the device answers on an ingest slot ---------------------------------------------------
    The batched ingest keeps a batch's frames, descriptors and records private to its slot, so a
@@ -955,6 +1013,16 @@ typedef struct emurx_answers {
 } emurx_answers;               /* 352 bytes */
 int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds);
 int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out);
+/* The timestamp reply on a slot.  emurx_ingest_set_answers_ts is emurx_ingest_set_answers with
+   kinds up to EMURX_RSPK_ALL_TS (EMURX_RSPK_TS without EMURX_RSPK_ICMP is EMURX_EINVAL); the slot's
+   chain then runs emurx_respond_ts_dev and emurx_nsstat_ts_dev.  emurx_ingest_set_time stores the
+   ip_time_ms the slot's next submits pass to the responder (each submit takes the value stored
+   at that moment, so two slots in flight carry their own times): a host store, no device work,
+   default 0; EMURX_EINVAL with a batch in flight on the slot or slot >= EMURX_INGEST_SLOTS.  The
+   sizing of the answer buffers holds: a timestamp reply is as long as its request, which is at
+   least 54 bytes (l4 + 20 <= len with l4 >= 34).  emurx_ingest_set_answers keeps rejecting 16. */
+int emurx_ingest_set_answers_ts(emurx_t* h, uint32_t slot, uint32_t kinds);
+int emurx_ingest_set_time(emurx_t* h, uint32_t slot, uint32_t ip_time_ms);
 
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);

@@ -33,7 +33,7 @@ GROUPS = [
     ("Mid-batch mutations", ["emurx_table_gen", "emurx_recs_stale"], "DESIGN.md §2.2, `dhcp.go:718`"),
     ("Batched ingest (primary)", ["emurx_ingest_buffer", "emurx_ingest_submit", "emurx_ingest_wait",
                                   "emurx_ingest_stream", "emurx_ingest_set_answers", "emurx_ingest_answers",
-                                  "emurx_zmq_walk_dev"],
+                                  "emurx_ingest_set_answers_ts", "emurx_ingest_set_time", "emurx_zmq_walk_dev"],
      "`VethIFZmq.OnRxStream` over the rx `select` loop's messages, `thread_ctx.go:409-410`, `veth_zmq.go:277-320`"),
     ("Receive path (device-resident; per-message fallback)",
      ["emurx_classify_dev", "emurx_parse_dev", "emurx_rx_stream", "emurx_zmq_descriptors",
@@ -50,12 +50,12 @@ GROUPS = [
      "(SURVEY §8e)"),
     ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev", "emurx_tx_zmq_counted_dev"],
      "gopacket checksum updates; `VethIFZmq.Send/FlushTx` `veth_zmq.go:149-200`"),
-    ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev"],
-     "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325`, `ipv6/ipv6.go:315-357`, "
-     "`NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
+    ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev", "emurx_respond_ts_dev"],
+     "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325` (echo and timestamp "
+     "reply), `ipv6/ipv6.go:315-357`, `NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),
     ("Device cache learning", ["emurx_learn_dev", "emurx_learn_max_events", "emurx_learn_key_hash"],
      "`PluginArpNs.ArpLearn` `arp/arp.go:886-901`, `NdLearn` `ipv6/nd.go:1611-1620`, `:1687-1776`"),
-    ("Device handler counters", ["emurx_nsstat_dev", "emurx_nsstat_max_events"],
+    ("Device handler counters", ["emurx_nsstat_dev", "emurx_nsstat_ts_dev", "emurx_nsstat_max_events"],
      "the counters of `HandleRxArpPacket` `arp/arp.go:904-946`, `HandleRxIcmpPacket` `icmp/icmp.go:396-462`, "
      "`HandleRxIpv6Packet` `ipv6/ipv6.go:465-539`, `HandleRxIpv6NdPacket` `ipv6/nd.go:1546-1776`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",

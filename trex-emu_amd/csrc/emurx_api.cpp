@@ -119,6 +119,7 @@ struct IngestSlot {
     // cfg.max_bytes; the per-frame outcome arrays join the result block (set_results)
     uint32_t ans_kinds = 0;               // the setting for later submits (EMURX_RSPK_*, 0: off)
     uint32_t ans_batch = 0;               // the kinds of the batch in flight / last waited for
+    uint32_t ans_time = 0;                // emurx_ingest_set_time: ip_time_ms of the slot's next submits
     bool waited = false;                  // a batch has been waited for
     uint64_t ans_rsp_cap = 0, ans_tx_cap = 0;
     uint32_t ans_r_cap = 0, ans_ev_cap = 0, ans_ns_cap = 0;
@@ -1528,14 +1529,16 @@ int emurx_tx_zmq_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
     return EMURX_OK;
 }
 
-// emurx_respond_dev and emurx_respond_kinds_dev: one implementation, the answers chosen by `kinds`
-// and the words of d_info that are written by `info_words`
+// emurx_respond_dev, emurx_respond_kinds_dev and emurx_respond_ts_dev: one implementation, the
+// answers chosen by `kinds` out of the entry point's `allowed`, the words of d_info that are
+// written by `info_words`; ip_time_ms is read for EMURX_RSPK_TS alone
 static int respond_kinds(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
-                         uint32_t n, uint32_t kinds, uint32_t info_words, uint8_t* d_out, uint64_t out_cap,
-                         emurx_desc* d_out_desc, uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+                         uint32_t n, uint32_t kinds, uint32_t allowed, uint32_t ip_time_ms, uint32_t info_words,
+                         uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t* d_out_src,
+                         uint8_t* d_outcome, uint64_t* d_info, void* stream) {
     if (!h || !d_info || (n && (!d_frames || !d_desc || !d_rec || !d_out_desc || !d_out_src || (!d_out && out_cap))))
         return EMURX_EINVAL;
-    if (kinds == 0 || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
+    if (kinds == 0 || (kinds & ~allowed)) return EMURX_EINVAL;
     if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_out & 15) || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) ||
         ((uintptr_t)d_out_desc & 7) || ((uintptr_t)d_info & 7))
         return EMURX_EINVAL;
@@ -1551,7 +1554,7 @@ static int respond_kinds(emurx_t* h, const uint8_t* d_frames, const emurx_desc* 
         if (h->d_rsp.alloc(need)) return EMURX_ENOMEM;
     }
     return emurx_launch_respond(d_frames, d_desc, d_rec, n, kinds, h->tables(), d_out, out_cap, d_out_desc, d_out_src,
-                                d_outcome, d_info, info_words, h->d_rsp.p, st)
+                                d_outcome, d_info, info_words, ip_time_ms, h->d_rsp.p, st)
                ? EMURX_EDEVICE
                : EMURX_OK;
 }
@@ -1559,15 +1562,22 @@ static int respond_kinds(emurx_t* h, const uint8_t* d_frames, const emurx_desc* 
 int emurx_respond_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
                       uint32_t n, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t* d_out_src,
                       uint8_t* d_outcome, uint64_t* d_info, void* stream) {
-    return respond_kinds(h, d_frames, d_desc, d_rec, n, EMURX_RSPK_ARP | EMURX_RSPK_ICMP | EMURX_RSPK_ICMPV6, 8, d_out,
-                         out_cap, d_out_desc, d_out_src, d_outcome, d_info, stream);
+    return respond_kinds(h, d_frames, d_desc, d_rec, n, EMURX_RSPK_ARP | EMURX_RSPK_ICMP | EMURX_RSPK_ICMPV6,
+                         EMURX_RSPK_ALL, 0, 8, d_out, out_cap, d_out_desc, d_out_src, d_outcome, d_info, stream);
 }
 
 int emurx_respond_kinds_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
                             uint32_t n, uint32_t kinds, uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc,
                             uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
-    return respond_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSP_INFO_WORDS, d_out, out_cap, d_out_desc, d_out_src,
-                         d_outcome, d_info, stream);
+    return respond_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSPK_ALL, 0, EMURX_RSP_INFO_WORDS, d_out, out_cap,
+                         d_out_desc, d_out_src, d_outcome, d_info, stream);
+}
+
+int emurx_respond_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                         uint32_t n, uint32_t kinds, uint32_t ip_time_ms, uint8_t* d_out, uint64_t out_cap,
+                         emurx_desc* d_out_desc, uint32_t* d_out_src, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    return respond_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSPK_ALL_TS, ip_time_ms, EMURX_RSP_INFO_WORDS, d_out,
+                         out_cap, d_out_desc, d_out_src, d_outcome, d_info, stream);
 }
 
 uint32_t emurx_learn_max_events(const emurx_t* h) { return h ? emurx_lrn_slots(h->cfg.max_frames) / 2 : 0; }
@@ -1607,11 +1617,14 @@ int emurx_learn_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_des
 
 uint32_t emurx_nsstat_max_events(const emurx_t* h) { return h ? std::min(h->cfg.max_frames, h->cfg.max_ns) : 0; }
 
-int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
-                     uint32_t kinds, const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome, emurx_nsstat_ev* d_ev,
-                     uint32_t ev_cap, uint8_t* d_done, uint64_t* d_info, void* stream) {
+// emurx_nsstat_dev and emurx_nsstat_ts_dev: one implementation, `kinds` out of the entry point's `allowed`
+static int nsstat_kinds(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                        uint32_t kinds, uint32_t allowed, const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome,
+                        emurx_nsstat_ev* d_ev, uint32_t ev_cap, uint8_t* d_done, uint64_t* d_info, void* stream) {
     if (!h || !d_info || !d_ev || (n && (!d_frames || !d_desc || !d_rec || !d_rsp_outcome))) return EMURX_EINVAL;
-    if (kinds == 0 || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
+    if (kinds == 0 || (kinds & ~allowed)) return EMURX_EINVAL;
+    // the timestamp rule refines the icmp handler's
+    if ((kinds & EMURX_RSPK_TS) && !(kinds & EMURX_RSPK_ICMP)) return EMURX_EINVAL;
     // the learn outcome decides for ARP and ND frames
     if (n && (kinds & (EMURX_RSPK_ARP | EMURX_RSPK_ND)) && !d_lrn_outcome) return EMURX_EINVAL;
     if (ev_cap == 0 || ev_cap > emurx_nsstat_max_events(h)) return EMURX_EINVAL;
@@ -1633,6 +1646,20 @@ int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_de
         return EMURX_EDEVICE;
     }
     return EMURX_OK;
+}
+
+int emurx_nsstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                     uint32_t kinds, const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome, emurx_nsstat_ev* d_ev,
+                     uint32_t ev_cap, uint8_t* d_done, uint64_t* d_info, void* stream) {
+    return nsstat_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSPK_ALL, d_rsp_outcome, d_lrn_outcome, d_ev, ev_cap,
+                        d_done, d_info, stream);
+}
+
+int emurx_nsstat_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                        uint32_t kinds, const uint8_t* d_rsp_outcome, const uint8_t* d_lrn_outcome, emurx_nsstat_ev* d_ev,
+                        uint32_t ev_cap, uint8_t* d_done, uint64_t* d_info, void* stream) {
+    return nsstat_kinds(h, d_frames, d_desc, d_rec, n, kinds, EMURX_RSPK_ALL_TS, d_rsp_outcome, d_lrn_outcome, d_ev, ev_cap,
+                        d_done, d_info, stream);
 }
 
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {
@@ -1678,7 +1705,7 @@ namespace {
 // What a batch of at most max_bytes message bytes can produce.  A frame the responder answers, or
 // the learner folds, has header offsets that fit it (l3 >= 14 and, for ARP, l3 + 28 <= len; the
 // other kinds need more), so it is at least 42 bytes long: at most max_bytes / 42 replies and
-// learn events.  A reply is the frame's own length (ICMP), shorter (ICMPv6), at most 50 bytes (ARP)
+// learn events.  A reply is the frame's own length (ICMP, the timestamp reply), shorter (ICMPv6), at most 50 bytes (ARP)
 // or at most 94 (ND), so align16(reply) <= max(align16(len), 96) <= len + 54 for len >= 42: the
 // replies take at most max_bytes * 96 / 42 bytes, and their framing 8 bytes per reply more.
 struct AnsCaps {
@@ -1709,8 +1736,10 @@ int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
     uint64_t* tx_info = rsp_info + EMURX_ANS_HEAD_TX;
     if (n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
     if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
-    int rc = respond_kinds(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, EMURX_RSP_INFO_WORDS, s.d_rsp_out.p,
-                           s.ans_rsp_cap, s.d_rsp_desc.p, s.d_rsp_src.p, s.d_rspo.p, rsp_info, st);
+    // the slot's time of day rides the launch as an argument: batches in flight keep their own
+    int rc = respond_kinds(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, EMURX_RSPK_ALL_TS, s.ans_time,
+                           EMURX_RSP_INFO_WORDS, s.d_rsp_out.p, s.ans_rsp_cap, s.d_rsp_desc.p, s.d_rsp_src.p, s.d_rspo.p,
+                           rsp_info, st);
     if (rc) return rc;
     if ((rc = emurx_tx_zmq_counted_dev(h, s.d_rsp_out.p, s.d_rsp_desc.p, n, rsp_info, s.d_tx.p, s.ans_tx_cap,
                                        s.d_tx_off.p, tx_info, st)))
@@ -1726,8 +1755,8 @@ int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
                  : EMURX_EDEVICE;
     }
     if (rc) return rc;
-    if ((rc = emurx_nsstat_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, s.d_rspo.p, s.d_lrno.p, s.d_nsev.p,
-                               emurx_nsstat_max_events(h), s.d_donef.p, nss_info, st)))
+    if ((rc = emurx_nsstat_ts_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, s.d_rspo.p, s.d_lrno.p, s.d_nsev.p,
+                                  emurx_nsstat_max_events(h), s.d_donef.p, nss_info, st)))
         return rc;
     // the shared scratch is free again: the next slot's stage may start while this one copies out
     if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
@@ -1754,12 +1783,10 @@ int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
     return emurx_launch_ans_out(a, n, st) ? EMURX_EDEVICE : EMURX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds) {
-    if (!h || slot >= EMURX_INGEST_SLOTS || (kinds & ~EMURX_RSPK_ALL)) return EMURX_EINVAL;
+// emurx_ingest_set_answers and emurx_ingest_set_answers_ts: `kinds` out of the entry point's `allowed`
+int set_answers(emurx_t* h, uint32_t slot, uint32_t kinds, uint32_t allowed) {
+    if (!h || slot >= EMURX_INGEST_SLOTS || (kinds & ~allowed)) return EMURX_EINVAL;
+    if ((kinds & EMURX_RSPK_TS) && !(kinds & EMURX_RSPK_ICMP)) return EMURX_EINVAL;
     int rc = bind(h);
     if (rc) return rc;
     IngestSlot& s = h->ing[slot];
@@ -1799,6 +1826,26 @@ int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds) {
     memset(s.h_ahead.p, 0, EMURX_ANS_HEAD_WORDS * sizeof(uint64_t));
     s.ans_rsp_cap = c.rsp, s.ans_tx_cap = c.tx, s.ans_r_cap = c.r, s.ans_ev_cap = c.ev, s.ans_ns_cap = c.ns;
     s.ans_kinds = kinds;
+    return EMURX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int emurx_ingest_set_answers(emurx_t* h, uint32_t slot, uint32_t kinds) {
+    return set_answers(h, slot, kinds, EMURX_RSPK_ALL);
+}
+
+int emurx_ingest_set_answers_ts(emurx_t* h, uint32_t slot, uint32_t kinds) {
+    return set_answers(h, slot, kinds, EMURX_RSPK_ALL_TS);
+}
+
+int emurx_ingest_set_time(emurx_t* h, uint32_t slot, uint32_t ip_time_ms) {
+    if (!h || slot >= EMURX_INGEST_SLOTS) return EMURX_EINVAL;
+    IngestSlot& s = h->ing[slot];
+    if (s.pending) return EMURX_EINVAL;
+    s.ans_time = ip_time_ms;
     return EMURX_OK;
 }
 

@@ -200,14 +200,15 @@ void emurx_comm_free(emurx_comm_state* c);   // emurx_comm.cpp: destroy a commun
 int emurx_launch_tx_csum(uint8_t* frames, const emurx_tx_desc* desc, uint32_t n, uint8_t* status,
                          hipStream_t st);
 
-// The device responder (emurx_respond.hip): see emurx_respond_dev / emurx_respond_kinds_dev.
-// kinds: EMURX_RSPK_*; info_words: 8 or EMURX_RSP_INFO_WORDS, the words of `info` that are written.
+// The device responder (emurx_respond.hip): see emurx_respond_dev / emurx_respond_kinds_dev /
+// emurx_respond_ts_dev.  kinds: EMURX_RSPK_*, EMURX_RSPK_TS among them; ip_time_ms: read for that
+// kind alone; info_words: 8 or EMURX_RSP_INFO_WORDS, the words of `info` that are written.
 // scratch: emurx_rsp_scratch_bytes(n), no initial state.  Three launches.
 size_t emurx_rsp_scratch_bytes(uint32_t n);
 int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
                          uint32_t kinds, const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc,
-                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, void* scratch,
-                         hipStream_t st);
+                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, uint32_t ip_time_ms,
+                         void* scratch, hipStream_t st);
 
 // The cache-learning fold (emurx_learn.hip): see emurx_learn_dev.  scratch:
 // emurx_lrn_scratch_bytes(max_frames), whose first emurx_lrn_slots(max_frames) * 16 bytes (the

@@ -7,7 +7,7 @@
 // unreachable 3 with codes Net 0 .. FragmentationNeeded 4, echo request 8, timestamp request 13;
 // layers/icmp6.go:21-52: destination unreachable 1 with codes 0..6, echo request 128, echo reply
 // 129, MLD 130..132 and 143, router solicitation 133 .. redirect 137).
-// emurx_nsstat_dev, three launches:
+// emurx_nsstat_dev / emurx_nsstat_ts_dev (the timestamp reply's two outcomes), three launches:
 //   k_nss_decide   one frame per lane: the record's second half says whether the frame is a
 //                  candidate; only a candidate's descriptor, its two outcome bytes, its ns_id and
 //                  the type / code / operation / destination-MAC / source bytes the rule names are
@@ -51,7 +51,7 @@ constexpr uint32_t kNssFirst = 1u << EMURX_NSC_ARP_QUERY | 1u << EMURX_NSC_ARP_R
                                1u << EMURX_NSC_ARP_ERR_WRONG_OP | 1u << EMURX_NSC_ICMP_ECHO | 1u << EMURX_NSC_ICMP_NO_CLIENT |
                                1u << EMURX_NSC_ICMP_ERR_MCAST | 1u << EMURX_NSC_ICMP_ERR_UNHANDLED | 1u << EMURX_NSC_V6_ECHO |
                                1u << EMURX_NSC_V6_NO_CLIENT | 1u << EMURX_NSC_V6_ERR_MCAST | 1u << EMURX_NSC_V6_ERR_UNHANDLED |
-                               1u << EMURX_NSC_ND_RX_NS | 1u << EMURX_NSC_ND_RX_NA;
+                               1u << EMURX_NSC_ND_RX_NS | 1u << EMURX_NSC_ND_RX_NA | 1u << EMURX_NSC_ICMP_ERR_TOO_SHORT;
 
 struct NssPlan {
     uint32_t done, cnt;  // cnt: the counters the frame bumps, a bit each (one of kNssFirst, at most one other)
@@ -66,7 +66,7 @@ __device__ __forceinline__ bool nss_candidate(const uint4& b, uint32_t kinds) {
     const uint32_t proto = b.z >> 24, status = b.w & 0xff;
     if (status != EMURX_ST_OK) return false;
     if (proto == EMURX_CB_ARP) return kinds & EMURX_RSPK_ARP;
-    if (proto == EMURX_CB_ICMP) return kinds & EMURX_RSPK_ICMP;
+    if (proto == EMURX_CB_ICMP) return kinds & EMURX_RSPK_ICMP;  // the timestamp kind comes with ICMP only
     return proto == EMURX_CB_ICMPV6 && (kinds & (EMURX_RSPK_ICMPV6 | EMURX_RSPK_ND));
 }
 
@@ -99,6 +99,10 @@ __device__ NssPlan nss_decide(const uint8_t* __restrict__ frames, const emurx_de
         if (lk != EMURX_LK_CLIENT) return nss_plan(0);
         if (ro == EMURX_RSP_DROP_MCAST) return nss_count(EMURX_NSC_ICMP_ERR_MCAST);
         if (ro == EMURX_RSP_ICMP) return nss_count(EMURX_NSC_ICMP_ECHO);
+        if (kinds & EMURX_RSPK_TS) {  // HandleEcho(ps, true): icmp.go:322-323, :313
+            if (ro == EMURX_RSP_TS) return nss_count(EMURX_NSC_ICMP_ECHO);
+            if (ro == EMURX_RSP_DROP_SHORT) return nss_count(EMURX_NSC_ICMP_ERR_TOO_SHORT);
+        }
         const uint32_t type = gld1(f + l4), code = gld1(f + l4 + 1);
         // echo request, timestamp request, echo reply, destination unreachable: the handler's
         if ((code == 0 && (type == 8 || type == 13 || type == 0)) || (type == 3 && code <= 4)) return nss_plan(0);

@@ -2,8 +2,10 @@
 // request for a client's IPv4 (src/emu/plugins/arp/arp.go:904-933 -> Respond :776-790), the
 // ICMPv4 echo reply (plugins/icmp/icmp.go:396-461 -> HandleEcho :289-325), the ICMPv6 echo
 // reply (plugins/ipv6/ipv6.go:465-504 -> HandleEcho :315-357) and the neighbour advertisement
-// to a neighbour solicitation (plugins/ipv6/nd.go:1546-1685 -> NdClientCtx.Respond :1220-1253).
-// emurx_respond_dev / emurx_respond_kinds_dev, three launches:
+// to a neighbour solicitation (plugins/ipv6/nd.go:1546-1685 -> NdClientCtx.Respond :1220-1253);
+// and, with the caller's time of day, the ICMPv4 timestamp reply (icmp.go:396-461 -> HandleEcho(ps,
+// true) :289-325, iptime :281-287, checksum layers/icmp4.go:252-256 over layers/tcpip.go:76-94).
+// emurx_respond_dev / emurx_respond_kinds_dev / emurx_respond_ts_dev, three launches:
 //   k_rsp_decide   one frame per lane: the record (32 B) says whether the frame is a candidate
 //                  (status OK; lookup EMURX_LK_CLIENT, callback arp / icmp / icmpv6; or lookup
 //                  EMURX_LK_NS_LEVEL, callback icmpv6: a neighbour solicitation if its type says
@@ -23,6 +25,12 @@
 //                  checksum, payload length, next header).  The ARP reply (42-50 B) and the
 //                  neighbour advertisement (86-94 B, six rows, checksummed in registers), both
 //                  built from their templates, are written by their frame's own lane.
+//                  A timestamp reply (kTs) is an echo reply's rows with eight more rewritten bytes
+//                  and a checksum over the rest of the frame, [l4, len): each row adds the 16-bit
+//                  halves of its patched bytes inside the span to the reply's LDS accumulator as
+//                  it is written, and behind a barrier the reply's own lane stores the checksum.
+// The kernels are templated on the kinds that need code of their own (kNd, kTs): a call without
+// them runs instantiations that hold none of it.
 // A batch without candidates costs the read of d_rec and one outcome byte per frame: the emit
 // workgroups of tiles without a reply leave after one 8-byte load.
 #include <hip/hip_runtime.h>
@@ -69,23 +77,27 @@ __device__ __forceinline__ IpHit rsp_probe_ip4(const emurx_dev_tables& T, uint32
 // The record's words (emurx_rec): ns, client, vlan0, vlan1, vport | l3 << 16, l4 | l7 << 16,
 // l7_len | next_hdr << 16 | proto << 24, status | flags << 8 | rsv << 16
 __device__ __forceinline__ uint32_t rsp_lk(const uint4& b) { return (b.w >> (8 + EMURX_FLAG_LK_SHIFT)) & 7u; }
-template <bool kNd>  // kNd: kinds has EMURX_RSPK_ND
+template <bool kNd, bool kTs>  // kNd: kinds has EMURX_RSPK_ND; kTs: EMURX_RSPK_TS
 __device__ __forceinline__ bool rsp_candidate(const uint4& b, uint32_t kinds) {
     const uint32_t proto = b.z >> 24, status = b.w & 0xff, lk = rsp_lk(b);
     if (status != EMURX_ST_OK) return false;
+    constexpr uint32_t kIcmp = kTs ? EMURX_RSPK_ICMP | EMURX_RSPK_TS : EMURX_RSPK_ICMP;  // the kinds the icmp callback serves
     if (lk == EMURX_LK_CLIENT)
-        return (proto == EMURX_CB_ARP && (kinds & EMURX_RSPK_ARP)) || (proto == EMURX_CB_ICMP && (kinds & EMURX_RSPK_ICMP)) ||
+        return (proto == EMURX_CB_ARP && (kinds & EMURX_RSPK_ARP)) || (proto == EMURX_CB_ICMP && (kinds & kIcmp)) ||
                (proto == EMURX_CB_ICMPV6 && (kinds & EMURX_RSPK_ICMPV6));
     return kNd && lk == EMURX_LK_NS_LEVEL && proto == EMURX_CB_ICMPV6;
 }
+template <bool kTs = false>
 __device__ __forceinline__ bool rsp_is_reply(uint32_t outcome) {
-    return (outcome >= EMURX_RSP_ARP && outcome <= EMURX_RSP_ICMPV6) || outcome == EMURX_RSP_ND;
+    return (outcome >= EMURX_RSP_ARP && outcome <= EMURX_RSP_ICMPV6) || outcome == EMURX_RSP_ND ||
+           (kTs && outcome == EMURX_RSP_TS);
 }
 
 // The decision for a candidate frame.  Header offsets that do not fit the frame (no record of
 // emurx_classify_dev for these descriptors has them) give EMURX_RSP_HOST: never guess.
+template <bool kTs>
 __device__ RspPlan rsp_decide(const uint8_t* __restrict__ frames, const emurx_desc& d, const uint4& a, const uint4& b,
-                              const emurx_dev_tables& T) {
+                              const emurx_dev_tables& T, uint32_t kinds) {
     const uint32_t proto = b.z >> 24, l3 = b.x >> 16, l4 = b.y & 0xffffu, len = d.len;
     const uint8_t* f = frames + d.off;
     if (d.pad == EMURX_DESC_HOLE) return {EMURX_RSP_NONE, 0};
@@ -103,8 +115,14 @@ __device__ RspPlan rsp_decide(const uint8_t* __restrict__ frames, const emurx_de
         if (l3 + 20 > len || l4 + 8 > len) return {EMURX_RSP_HOST, 0};
         if (!rsp_ip4_src_ok(rsp_le32(f + l3 + 12))) return {EMURX_RSP_DROP_MCAST, 0};  // icmp.go:429-436
         const uint32_t tc = gld1(f + l4) << 8 | gld1(f + l4 + 1);
-        if (tc == 0x0d00u) return {EMURX_RSP_HOST, 0};  // timestamp request: wall-clock time
-        if (tc != 0x0800u) return {EMURX_RSP_NONE, 0};
+        if (tc == 0x0d00u) {  // timestamp request: the time of day is the caller's (kTs), else the handler's
+            if (!kTs || !(kinds & EMURX_RSPK_TS)) return {EMURX_RSP_HOST, 0};
+            if (group_src) return {EMURX_RSP_DROP_MCAST, 0};          // icmp.go:295-299
+            if (len - l4 < 20) return {EMURX_RSP_DROP_SHORT, 0};      // :312-316, behind the multicast test
+            if (l4 & 1u) return {EMURX_RSP_HOST, 0};  // no parse of ours: the rows sum on the 16-bit grid
+            return {EMURX_RSP_TS, len};
+        }
+        if (tc != 0x0800u || (kTs && !(kinds & EMURX_RSPK_ICMP))) return {EMURX_RSP_NONE, 0};
         if (group_src) return {EMURX_RSP_DROP_MCAST, 0};
         return {EMURX_RSP_ICMP, len};
     }
@@ -138,12 +156,14 @@ __device__ RspPlan rsp_decide_nd(const uint8_t* __restrict__ frames, const emurx
         });
 }
 
-// tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows.
+// tile sums: x = replies | DROP_MCAST << 10 | HOST << 20 (each <= 256), y = the replies' 16-byte rows
+// (at most 256 * 576 < 2^18); with kTs, y also carries DROP_SHORT << 20 (kRspRowBits).
 // kNd: whether the call answers solicitations; without them (emurx_respond_dev) the kernel holds
 // none of that path.  Eight waves per SIMD asked for: left to itself the compiler spends 106 SGPRs
 // on the nested divergent branches of the (cold) solicitation path, one wave per SIMD less for
 // every batch.
-template <bool kNd>
+constexpr uint32_t kRspRowBits = 20, kRspRowMask = (1u << kRspRowBits) - 1u;
+template <bool kNd, bool kTs>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_rsp_decide(
     const uint8_t* __restrict__ frames, const emurx_desc* __restrict__ desc, const emurx_rec* __restrict__ rec, uint32_t n,
     uint32_t kinds, const emurx_dev_tables T, uint32_t* __restrict__ plan, uint2* __restrict__ tsum,
@@ -155,17 +175,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     RspPlan p{EMURX_RSP_NONE, 0};
     if (i < n) {
         const uint4 b = gld16(reinterpret_cast<const uint4*>(rec + i) + 1);
-        if (rsp_candidate<kNd>(b, kinds)) {
+        if (rsp_candidate<kNd, kTs>(b, kinds)) {
             const uint4 a = gld16(reinterpret_cast<const uint4*>(rec + i));
-            if (!kNd || rsp_lk(b) == EMURX_LK_CLIENT) p = rsp_decide(frames, desc[i], a, b, T);
+            if (!kNd || rsp_lk(b) == EMURX_LK_CLIENT) p = rsp_decide<kTs>(frames, desc[i], a, b, T, kinds);
             else p = rsp_decide_nd(frames, desc[i], a, b, T);
         }
         if (outcome) outcome[i] = (uint8_t)p.outcome;
     }
-    const bool reply = rsp_is_reply(p.outcome);
+    const bool reply = rsp_is_reply<kTs>(p.outcome);
     const uint32_t c = wave_sum_u32((reply ? 1u : 0u) | (p.outcome == EMURX_RSP_DROP_MCAST ? 1u << 10 : 0u) |
                                     (p.outcome == EMURX_RSP_HOST ? 1u << 20 : 0u));
-    const uint32_t r = wave_sum_u32(reply ? (p.len + 15) >> 4 : 0u);
+    const uint32_t r = wave_sum_u32((reply ? (p.len + 15) >> 4 : 0u) |
+                                    (kTs && p.outcome == EMURX_RSP_DROP_SHORT ? 1u << kRspRowBits : 0u));
     if (lane_id() == 0 && (c | r)) {
         atomicAdd(&s_sum[0], c);
         atomicAdd(&s_sum[1], r);
@@ -176,23 +197,28 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     if ((s_sum[0] & 0x3ffu) && i < n) plan[i] = p.outcome << 16 | p.len;
 }
 
-// info: {n_out, bytes needed, count of outcomes 1..7, zeros}, info_words (8 or
-// EMURX_RSP_INFO_WORDS) of them: the scan writes bytes needed, DROP_MCAST and HOST and zeroes the
-// rest; the emit pass adds n_out, the replies by kind and NOSPC
+// info: {n_out, bytes needed, count of outcomes 1..9, zeros}, info_words (8 or
+// EMURX_RSP_INFO_WORDS) of them: the scan writes bytes needed, DROP_MCAST, HOST and (kTs)
+// DROP_SHORT and zeroes the rest; the emit pass adds n_out, the replies by kind and NOSPC
+template <bool kTs>
 __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restrict__ tsum, uint32_t ntiles,
                                                             uint32_t* __restrict__ tord,
                                                             unsigned long long* __restrict__ trow,
                                                             unsigned long long* __restrict__ info, uint32_t info_words) {
     __shared__ BlockScanLds<kRspScanBlock, uint32_t, unsigned long long> s_scan;
-    __shared__ uint32_t s_dh[2];
-    if (threadIdx.x < 2) s_dh[threadIdx.x] = 0;
-    uint32_t cbase = 0, drop = 0, host = 0;
+    __shared__ uint32_t s_dh[kTs ? 3 : 2];
+    if (threadIdx.x < (kTs ? 3 : 2)) s_dh[threadIdx.x] = 0;
+    uint32_t cbase = 0, drop = 0, host = 0, shrt = 0;
     // rows are counted in 64 bits (r, the round's total and rbase): a batch of fewer than 2^26
     // jumbo echo requests (576 rows each) can hold more than 2^32 of them
     unsigned long long rbase = 0;
     for (uint32_t t0 = 0; t0 < ntiles; t0 += kRspScanBlock) {  // workgroup-uniform trip count
         const uint32_t t = t0 + threadIdx.x;
-        const uint2 v = t < ntiles ? tsum[t] : make_uint2(0, 0);
+        uint2 v = t < ntiles ? tsum[t] : make_uint2(0, 0);
+        if (kTs) {
+            shrt += v.y >> kRspRowBits;
+            v.y &= kRspRowMask;
+        }
         const uint32_t cnt = v.x & 0x3ffu;
         drop += (v.x >> 10) & 0x3ffu;
         host += v.x >> 20;
@@ -208,15 +234,18 @@ __global__ __launch_bounds__(kRspScanBlock) void k_rsp_scan(const uint2* __restr
     }
     drop = wave_sum_u32(drop);
     host = wave_sum_u32(host);
+    if (kTs) shrt = wave_sum_u32(shrt);
     __syncthreads();
     if (lane_id() == 0) {
         atomicAdd(&s_dh[0], drop);
         atomicAdd(&s_dh[1], host);
+        if (kTs) atomicAdd(&s_dh[2], shrt);
     }
     __syncthreads();
     if (threadIdx.x < info_words) {
         const uint32_t k = threadIdx.x;
-        info[k] = k == 1 ? rbase * 16ull : k == 2 + EMURX_RSP_DROP_MCAST - 1 ? s_dh[0] : k == 2 + EMURX_RSP_HOST - 1 ? s_dh[1] : 0ull;
+        info[k] = k == 1 ? rbase * 16ull : k == 2 + EMURX_RSP_DROP_MCAST - 1 ? s_dh[0] : k == 2 + EMURX_RSP_HOST - 1 ? s_dh[1]
+                  : kTs && k == 2 + EMURX_RSP_DROP_SHORT - 1 ? s_dh[kTs ? 2 : 0] : 0ull;
     }
 }
 
@@ -246,6 +275,28 @@ struct RspReply {
     uint32_t cs;     // the new checksum | the new IPv6 payload length << 16
 };
 
+// the reply whose rows hold row x of the tile: the last k with s_row[k] <= x
+__device__ __forceinline__ uint32_t rsp_row_owner(const uint32_t* s_row, uint32_t replies, uint32_t x) {
+    uint32_t lo = 0, hi = replies;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_row[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// A timestamp reply's rewritten ICMP bytes in the row that starts at y0 (icmp.go:310-319): type 14,
+// the checksum field zero (UpdateChecksum zeroes it before it sums, layers/icmp4.go:252-256),
+// receive and transmit timestamp = ipt, big-endian.  The eight time bytes may straddle two rows.
+__device__ __forceinline__ void rsp_ts_patch(uint32_t o[4], uint32_t y0, uint32_t l4, uint32_t ipt) {
+    rsp_set_byte(o, y0, l4, 14u);
+    rsp_set_byte(o, y0, l4 + 2, 0u);
+    rsp_set_byte(o, y0, l4 + 3, 0u);
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) rsp_set_byte(o, y0, l4 + 12 + j, (ipt >> (24 - 8 * (j & 3))) & 0xff);
+}
+
+template <bool kTs>
 __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__ frames,
                                                      const emurx_desc* __restrict__ desc,
                                                      const emurx_rec* __restrict__ rec, uint32_t n,
@@ -254,24 +305,31 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
                                                      const unsigned long long* __restrict__ trow,
                                                      uint8_t* __restrict__ out, unsigned long long cap,
                                                      emurx_desc* __restrict__ odesc, uint32_t* __restrict__ osrc,
-                                                     uint8_t* __restrict__ outcome, unsigned long long* __restrict__ info) {
-    __shared__ BlockScanLds<kBlock, uint32_t, uint32_t> s_scan;
+                                                     uint8_t* __restrict__ outcome, unsigned long long* __restrict__ info,
+                                                     uint32_t ipt) {
+    __shared__ alignas(16) BlockScanLds<kBlock, uint32_t, uint32_t> s_scan;  // aligned: its 8-byte pairs are stored whole
     __shared__ uint32_t s_row[kRspTile + 1];  // first row (in the tile) of reply k; [replies] = the tile's rows
     __shared__ RspReply s_rep[kRspTile];
     __shared__ uint32_t s_mac[kRspTile][3];   // an echo reply's first 12 bytes: the Ethernet addresses swapped
     __shared__ uint32_t s_ip[kRspTile][10];   // its IP addresses swapped (8 or 32 bytes) between two pad dwords
-    __shared__ uint32_t s_cnt[8];             // by outcome: written replies by kind (1..3, 7), NOSPC (6)
+    constexpr uint32_t kCnt = kTs ? 9 : 8;
+    // by outcome: written replies by kind (1..3, 7, 8), NOSPC (6); with kTs, from word 16 on, per
+    // reply of the tile a timestamp reply's sum of 16-bit halves over [l4, len) (one array: the
+    // instantiation without kTs keeps its LDS layout)
+    __shared__ uint32_t s_cnt[kTs ? 16 + kRspTile : 8];
+    uint32_t* const s_acc = s_cnt + (kTs ? 16 : 0);
     const uint32_t t = blockIdx.x;
-    const uint2 ts = tsum[t];
+    uint2 ts = tsum[t];
+    if (kTs) ts.y &= kRspRowMask;
     const uint32_t replies = ts.x & 0x3ffu;
     if (!replies) return;  // workgroup-uniform
     const uint32_t i = t * kRspTile + threadIdx.x;
-    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < kCnt) s_cnt[threadIdx.x] = 0;
     const uint32_t ord0 = tord[t];
     const unsigned long long row0 = trow[t];
     const uint32_t p = i < n ? plan[i] : 0u;
     const uint32_t kind = p >> 16, rlen = p & 0xffffu;
-    const bool reply = rsp_is_reply(kind);
+    const bool reply = rsp_is_reply<kTs>(kind);
     const uint32_t rows = reply ? (rlen + 15) >> 4 : 0u;
     // ordinal and first row inside the tile (the one scan of this launch: kAgain = false)
     uint32_t k = reply ? 1u : 0u, r = rows;
@@ -283,6 +341,7 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
     // offset); offsets ascend, so the replies that fit are a prefix and keep their ordinals
     const unsigned long long off = (row0 + r) * 16ull, end = off + 16ull * rows;
     const bool fits = end <= cap && end <= (1ull << 32);
+    uint32_t tsfix = 0;  // a timestamp reply written: the offset of its checksum in `out` (never 0: off + l4 + 2)
     if (reply) {
         const uint4 a = gld16(reinterpret_cast<const uint4*>(rec + i));
         const uint4 b = gld16(reinterpret_cast<const uint4*>(rec + i) + 1);
@@ -407,6 +466,8 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
                 if (kind == EMURX_RSP_ICMPV6)  // PayloadLength() - optionbytes, uint16 (ipv6.go:335)
                     plen = ((gld1(f + l3 + 4) << 8 | gld1(f + l3 + 5)) - (l4 - l4n)) & 0xffffu;
                 e.cs = ncs | plen << 16;
+                if (kTs) s_acc[k] = 0;
+                if (kTs && kind == EMURX_RSP_TS) tsfix = (uint32_t)off + l4 + 2;  // even: l4 is, off a multiple of 16
                 e.lens |= kind << 16;
                 // the swapped addresses, once per reply: Ethernet (row 0's first 12 bytes) and IP
                 const uintptr_t Fa = (uintptr_t)f;
@@ -434,24 +495,28 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
         atomicAdd(&s_cnt[fits ? kind : (uint32_t)EMURX_RSP_NOSPC], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 8) {  // info[1 + outcome] counts the outcome; info[0] = the replies written
+    if (threadIdx.x < kCnt) {  // info[1 + outcome] counts the outcome; info[0] = the replies written
         // (ND is no outcome of the eight-word form: its count is 0 there and info[8] is not touched)
         const uint32_t j = threadIdx.x;
-        const uint32_t c = j ? s_cnt[j] : s_cnt[EMURX_RSP_ARP] + s_cnt[EMURX_RSP_ICMP] + s_cnt[EMURX_RSP_ICMPV6] + s_cnt[EMURX_RSP_ND];
+        const uint32_t c = j ? s_cnt[j]
+                             : s_cnt[EMURX_RSP_ARP] + s_cnt[EMURX_RSP_ICMP] + s_cnt[EMURX_RSP_ICMPV6] + s_cnt[EMURX_RSP_ND] +
+                                   (kTs ? s_cnt[kTs ? EMURX_RSP_TS : 0] : 0u);
         if (c) atomicAdd(&info[j ? 1u + j : 0u], (unsigned long long)c);
     }
-    // ---- the echo replies' rows, dealt over the lanes
     const uint32_t R = ts.y;
+    // ---- the echo (and timestamp) replies' rows, dealt over the lanes.
+    // A timestamp reply's checksum covers the rest of the frame, [l4, len), so it is known only once
+    // every row of the reply has been seen: its rows go out with the checksum field zero and add the
+    // sum of the 16-bit halves of their bytes inside the span to the reply's accumulator; behind a
+    // barrier the reply's own lane stores the two checksum bytes (below).  l4 is even and a row
+    // starts at a multiple of 16, so a little-endian half is a byte-swapped pair of tcpipChecksum
+    // (layers/tcpip.go:76-94), an odd last byte lands in the pair's high byte once swapped, and a
+    // u32 holds the sum of any frame a u16 length describes (32,768 halves).
     for (uint32_t x = threadIdx.x; x < R; x += kBlock) {
-        uint32_t lo = 0, hi = replies;  // the reply whose rows hold x: the last k with s_row[k] <= x
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s_row[mid] <= x) lo = mid;
-            else hi = mid;
-        }
+        const uint32_t lo = rsp_row_owner(s_row, replies, x);
         const RspReply e = s_rep[lo];
         const uint32_t ek = e.lens >> 16;
-        if (ek != EMURX_RSP_ICMP && ek != EMURX_RSP_ICMPV6) continue;  // ARP, or no room
+        if (ek != EMURX_RSP_ICMP && ek != EMURX_RSP_ICMPV6 && !(kTs && ek == EMURX_RSP_TS)) continue;  // ARP, or no room
         const bool v6 = ek == EMURX_RSP_ICMPV6;
         const uint32_t flen = e.lens & 0xffffu, l3 = e.l3l4 & 0xffffu, l4 = e.l3l4 >> 16;
         const uint32_t strip = v6 ? l4 - l3 - 40 : 0u;
@@ -482,15 +547,33 @@ __global__ __launch_bounds__(kBlock) void k_rsp_emit(const uint8_t* __restrict__
             }
         }
         const uint32_t tpos = v6 ? l3 + 40 : l4;
-        rsp_set_byte(o, y0, tpos, v6 ? 129u : 0u);
-        rsp_set_byte(o, y0, tpos + 2, (e.cs >> 8) & 0xff);
-        rsp_set_byte(o, y0, tpos + 3, e.cs & 0xff);
+        if (kTs && ek == EMURX_RSP_TS) {
+            rsp_ts_patch(o, y0, l4, ipt);
+            if (y0 + 16 > l4) {  // the patched bytes of this row that lie in [l4, len)
+                const int b0 = max((int)l4 - (int)y0, 0), b1 = min((int)flen - (int)y0, 16);
+                uint32_t acc = 0;
+#pragma unroll
+                for (int dw = 0; dw < 4; ++dw) acc = sad16(o[dw] & rsp_bytes(b0, b1, dw), acc);
+                atomicAdd(&s_acc[lo], acc);
+            }
+        } else {
+            rsp_set_byte(o, y0, tpos, v6 ? 129u : 0u);
+            rsp_set_byte(o, y0, tpos + 2, (e.cs >> 8) & 0xff);
+            rsp_set_byte(o, y0, tpos + 3, e.cs & 0xff);
+        }
         if (strip) {
             rsp_set_byte(o, y0, l3 + 4, e.cs >> 24);
             rsp_set_byte(o, y0, l3 + 5, (e.cs >> 16) & 0xff);
             rsp_set_byte(o, y0, l3 + 6, 58u);
         }
         *reinterpret_cast<uint4*>(out + (row0 + x) * 16ull) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    // ---- the timestamp replies' checksums: only a tile that wrote such a reply comes here
+    if (kTs && s_cnt[kTs ? EMURX_RSP_TS : 0]) {  // workgroup-uniform
+        __syncthreads();  // every row's sum is in, and every row's store is ordered before the store below
+        // the complement of the folded sum, still in the halves' byte order: one 16-bit store puts
+        // its low byte first, the checksum's first byte in memory (a folded sum of 0xffff stores 0x0000)
+        if (tsfix) *reinterpret_cast<uint16_t*>(out + tsfix) = (uint16_t)(~fold16(s_acc[k]) & 0xffffu);
     }
 }
 
@@ -513,20 +596,25 @@ size_t emurx_rsp_scratch_bytes(uint32_t n) { return rsp_scratch(nullptr, n).byte
 
 int emurx_launch_respond(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n,
                          uint32_t kinds, const emurx_dev_tables& T, uint8_t* out, uint64_t cap, emurx_desc* out_desc,
-                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, void* scratch,
-                         hipStream_t st) {
+                         uint32_t* out_src, uint8_t* outcome, uint64_t* info, uint32_t info_words, uint32_t ip_time_ms,
+                         void* scratch, hipStream_t st) {
     using namespace emurx;
     unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
     if (n == 0) return EMURX_HIP_OK(hipMemsetAsync(inf, 0, 8 * (size_t)info_words, st)) ? 0 : -1;
     const uint32_t nt = (n + kRspTile - 1) / kRspTile;
     const RspScratch s = rsp_scratch(scratch, n);
-    const auto decide = (kinds & EMURX_RSPK_ND) ? k_rsp_decide<true> : k_rsp_decide<false>;
+    // a call without the timestamp kind runs the instantiations that hold none of its code
+    const bool nd = kinds & EMURX_RSPK_ND, tsk = kinds & EMURX_RSPK_TS;
+    const auto decide = tsk ? (nd ? k_rsp_decide<true, true> : k_rsp_decide<false, true>)
+                            : (nd ? k_rsp_decide<true, false> : k_rsp_decide<false, false>);
     hipError_t e = emurx_launch(decide, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, kinds, T, s.plan, s.tsum,
                                 outcome);
     if (e == hipSuccess)
-        e = emurx_launch(k_rsp_scan, dim3(1), dim3(kRspScanBlock), 0, st, s.tsum, nt, s.tord, s.trow, inf, info_words);
+        e = emurx_launch(tsk ? k_rsp_scan<true> : k_rsp_scan<false>, dim3(1), dim3(kRspScanBlock), 0, st, s.tsum, nt, s.tord,
+                         s.trow, inf, info_words);
     if (e == hipSuccess)
-        e = emurx_launch(k_rsp_emit, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T, s.plan, s.tsum, s.tord,
-                         s.trow, out, (unsigned long long)cap, out_desc, out_src, outcome, inf);
+        e = emurx_launch(tsk ? k_rsp_emit<true> : k_rsp_emit<false>, dim3(nt), dim3(kBlock), 0, st, frames, desc, rec, n, T,
+                         s.plan, s.tsum, s.tord, s.trow, out, (unsigned long long)cap, out_desc, out_src, outcome, inf,
+                         ip_time_ms);
     return EMURX_HIP_OK(e) ? 0 : -1;
 }

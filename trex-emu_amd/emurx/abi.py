@@ -114,8 +114,11 @@ TX_ZMQ_MAX_FRAMES = 1 << 26  # EMURX_TX_ZMQ_MAX_FRAMES: n of tx_zmq_dev / respon
 # enum emurx_rsp: the per-frame outcome of emurx_respond_dev
 RSP_NONE, RSP_ARP, RSP_ICMP, RSP_ICMPV6, RSP_DROP_MCAST, RSP_HOST, RSP_NOSPC = range(7)
 RSP_ND = 7  # neighbour advertisement written (emurx_respond_kinds_dev with RSPK_ND)
+# emurx_respond_ts_dev with RSPK_TS: timestamp reply written; len - l4 < 20 (pktRxErrTooShort, nothing sent)
+RSP_TS, RSP_DROP_SHORT = 8, 9
 # EMURX_RSPK_*: the answers emurx_respond_kinds_dev is asked for; its d_info has RSP_INFO_WORDS words
 RSPK_ARP, RSPK_ICMP, RSPK_ICMPV6, RSPK_ND, RSPK_ALL = 1, 2, 4, 8, 15
+RSPK_TS, RSPK_ALL_TS = 16, 31  # the ICMPv4 timestamp reply: the *_ts entry points only
 RSP_INFO_WORDS = 16
 # enum emurx_lrn: the per-frame outcome of emurx_learn_dev; 1..4 are also the kinds of its events
 LRN_NONE, LRN_ARP_REQ, LRN_ARP_REPLY, LRN_ND_NS, LRN_ND_NA, LRN_HOST = range(6)
@@ -132,6 +135,7 @@ assert LEARN_EV_DTYPE.itemsize == 40
  NSC_ICMP_ECHO, NSC_ICMP_NO_CLIENT, NSC_ICMP_ERR_MCAST, NSC_ICMP_ERR_UNHANDLED, NSC_V6_ECHO, NSC_V6_NO_CLIENT,
  NSC_V6_ERR_MCAST, NSC_V6_ERR_UNHANDLED, NSC_ND_RX_NS, NSC_ND_TX_ADV_UNICAST, NSC_ND_TX_DAD_ERROR, NSC_ND_RX_NA,
  NSC_ND_RX_NA_LEARN) = range(19)
+NSC_ICMP_ERR_TOO_SHORT = 19  # IcmpNsStats.pktRxErrTooShort (emurx_nsstat_ts_dev)
 NSC_WORDS = 22
 NSS_INFO_WORDS = 8
 # the Go counters of each word: (plugin stats, names)
@@ -143,6 +147,8 @@ NSC_GO = [("arp", ("pktRxArpQuery",)), ("arp", ("pktRxArpQueryNotForUs",)), ("ar
           ("ipv6", ("pktRxErrMulticastB",)), ("ipv6", ("pktRxErrUnhandled",)),
           ("nd", ("pktRxNeighborSolicitation",)), ("nd", ("pktTxNeighborAdvUnicast",)), ("nd", ("pktTxNeighborDADError",)),
           ("nd", ("pktRxNeighborAdvertisement",)), ("nd", ("pktRxNeighborAdvLearn",))]
+# the same with the word emurx_nsstat_ts_dev adds (NSC_ICMP_ERR_TOO_SHORT)
+NSC_GO_TS = NSC_GO + [("icmp", ("pktRxErrTooShort",))]
 # emurx_nsstat_ev: one event per Namespace with a frame whose handler is not needed
 NSSTAT_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("frames", "<u4"), ("cnt", "<u4", NSC_WORDS)])
 assert NSSTAT_EV_DTYPE.itemsize == 96
@@ -268,16 +274,21 @@ SIGNATURES = [
     ("emurx_ingest_stream", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("emurx_ingest_set_answers", C.c_int, [_P, C.c_uint32, C.c_uint32]),
     ("emurx_ingest_answers", C.c_int, [_P, C.c_uint32, C.POINTER(Answers)]),
+    ("emurx_ingest_set_answers_ts", C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    ("emurx_ingest_set_time", C.c_int, [_P, C.c_uint32, C.c_uint32]),
     ("emurx_tx_checksum_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_tx_zmq_counted_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("emurx_respond_ts_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P,
+                                       _P]),
     ("emurx_learn_max_events", C.c_uint32, [_P]),
     ("emurx_learn_key_hash", C.c_uint32, [_P]),
     ("emurx_learn_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("emurx_nsstat_max_events", C.c_uint32, [_P]),
     ("emurx_nsstat_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_nsstat_ts_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -297,7 +308,8 @@ SIGNATURES = [
 
 # measurement observables that an older library given through EMURX_LIB (A/B runs of one
 # bench.py against two builds) may lack; calling one it lacks is an AttributeError
-OPTIONAL = {"emurx_last_uniform", "emurx_last_trim"}
+OPTIONAL = {"emurx_last_uniform", "emurx_last_trim", "emurx_respond_ts_dev", "emurx_nsstat_ts_dev",
+            "emurx_ingest_set_answers_ts", "emurx_ingest_set_time"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
 TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 

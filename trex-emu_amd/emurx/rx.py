@@ -262,7 +262,15 @@ class RxPath:
     def ingest_set_answers(self, slot: int, kinds: int) -> None:
         """Run the device answer chain (respond, tx framing, learn, nsstat) on the slot's later
         batches: kinds abi.RSPK_* bits, 0 turns it off (include/emu_rx.h emurx_ingest_set_answers)."""
+        if kinds & abi.RSPK_TS:  # the timestamp reply: its own entry point (the slot's time: ingest_set_time)
+            abi.check(self.lib.emurx_ingest_set_answers_ts(self.h, slot, kinds), "ingest_set_answers_ts")
+            return
         abi.check(self.lib.emurx_ingest_set_answers(self.h, slot, kinds), "ingest_set_answers")
+
+    def ingest_set_time(self, slot: int, ip_time: int) -> None:
+        """The time of day (milliseconds since midnight UTC, the reference's iptime()) that the
+        slot's next submits put into timestamp replies (include/emu_rx.h emurx_ingest_set_time)."""
+        abi.check(self.lib.emurx_ingest_set_time(self.h, slot, ip_time & 0xFFFFFFFF), "ingest_set_time")
 
     def ingest_answers(self, slot: int, n_frames: int) -> dict:
         """The answers of the slot's batch, after its ingest_wait (n_frames: that result's n), as
@@ -307,14 +315,21 @@ class RxPath:
                                                            _stream(stream)), "tx_zmq_counted_dev")
 
     def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None,
-                    kinds=None):
+                    kinds=None, ip_time=None):
         """The ARP / ICMPv4 echo / ICMPv6 echo replies of a classified batch, built on the device
         (include/emu_rx.h emurx_respond_dev): replies compacted in rx order into `out` at 16-byte
         aligned offsets, out_desc / out_src [n] (the descriptors tx_zmq_dev takes, the rx frame
         index), outcome u8 [n] (abi.RSP_*, or None), info u64[8] {n_out, bytes needed, frames per
         outcome 1..6}.  With kinds (abi.RSPK_*, emurx_respond_kinds_dev) only the selected answers
         are built, the neighbour advertisement (RSPK_ND) among them, and info is
-        u64[abi.RSP_INFO_WORDS] {n_out, bytes needed, frames per outcome 1..7, zeros}."""
+        u64[abi.RSP_INFO_WORDS] {n_out, bytes needed, frames per outcome 1..7, zeros}.  With ip_time
+        (milliseconds since midnight UTC; emurx_respond_ts_dev) kinds may hold RSPK_TS: timestamp
+        requests are answered with that time, and info counts the outcomes 1..9."""
+        if ip_time is not None:
+            return abi.check(self.lib.emurx_respond_ts_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n,
+                                                           abi.RSPK_ALL_TS if kinds is None else kinds, ip_time & 0xFFFFFFFF,
+                                                           _addr(out), cap, _addr(out_desc), _addr(out_src), _addr(outcome),
+                                                           _addr(info), _stream(stream)), "respond_ts_dev")
         if kinds is None:
             return abi.check(self.lib.emurx_respond_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, _addr(out), cap,
                                                         _addr(out_desc), _addr(out_src), _addr(outcome), _addr(info),
@@ -350,7 +365,12 @@ class RxPath:
         ns_id; done u8 [n] (0 the Go handler runs, 1 skip it, 2 skip it and count errParser; or
         None); info u64[abi.NSS_INFO_WORDS] {events written, distinct Namespaces, overflow, frames
         done 1, done 2, candidates left at 0, 0, 0}.  On overflow (distinct > ev_cap) no event is
-        written."""
+        written.  With RSPK_TS in kinds (emurx_nsstat_ts_dev) rsp_outcome is that of
+        respond_dev(kinds=..., ip_time=...)."""
+        if kinds & abi.RSPK_TS:
+            return abi.check(self.lib.emurx_nsstat_ts_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds,
+                                                          _addr(rsp_outcome), _addr(lrn_outcome), _addr(ev), ev_cap,
+                                                          _addr(done), _addr(info), _stream(stream)), "nsstat_ts_dev")
         return abi.check(self.lib.emurx_nsstat_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds,
                                                    _addr(rsp_outcome), _addr(lrn_outcome), _addr(ev), ev_cap, _addr(done),
                                                    _addr(info), _stream(stream)), "nsstat_dev")
