@@ -958,6 +958,103 @@ int emurx_nsstat_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d
                         emurx_nsstat_ev* d_ev, uint32_t ev_cap,
                         uint8_t* d_done, uint64_t* d_info, void* stream);
 
+/* ---- echo replies and destination-unreachable messages, folded per ping ------------------------
+   The rx half of icmp_c_start_ping / ipv6_start_ping: an ICMPv4 echo reply (0,0) or destination
+   unreachable (3,0..4) reaches PluginIcmpNs.HandleEchoReply / HandleDestinationUnreachable
+   (plugins/icmp/icmp.go:328-393, from HandleRxIcmpPacket :396-462), an ICMPv6 echo reply (129,0) or
+   destination unreachable (1,0..6) PluginIpv6Ns.HandleEchoReply / HandleDestinationUnreachable
+   (plugins/ipv6/ipv6.go:359-462, from :517-532); both hand the frame to the client's Ping
+   (icmp.go:180-203, ipv6.go:188-210; plugins/ping/ping.go:246-311).  emurx_nsstat_dev leaves these
+   frames at done 0.  All a frame does there is bump counters and advance a small per-ping state,
+   and only the in-order test and the minimum-latency rule depend on frame order, among the
+   frames of one ping: emurx_ping_dev folds a batch's frames into one event per {ns_id, client_id,
+   family, identifier}.  The identifier is the one on the wire: whether the client has a ping
+   running and whether the identifier is its own is decided when Go replays the event, so no
+   mid-batch change of the ping state can make the device's view stale.
+   d_rec: the records emurx_classify_dev wrote for d_frames / d_desc on this handle.  fams:
+   EMURX_PNGK_* bits.  now_unix_ns: the caller's time.Now().UnixNano(), one value per batch (the
+   contract of emurx_respond_ts_dev's ip_time_ms), below 2^63; the reference's simulation uses
+   128 + 1,000,000 (ping.go:263-265).
+   A frame is a candidate if rec.status == EMURX_ST_OK, its descriptor is no hole and its callback
+   is icmp with fams & EMURX_PNGK_V4 or icmpv6 with fams & EMURX_PNGK_V6; every other frame gets
+   EMURX_PNG_NONE.  Before any byte of a candidate is read, the header offsets (emurx_nsstat_dev's
+   tests): icmp l3 < 14, l3 + 20 > len or l4 + 8 > len; icmpv6 l3 < 14, l3 + 40 > l4 or l4 + 4 >
+   len: each gives EMURX_PNG_HOST.  Then
+     icmp    lookup other than CLIENT / CLIENT_NO_PLUGIN -> NONE (NO_CLIENT is emurx_nsstat_dev's
+             pktRxNoClientUnhandled).  Type, code p[l4], p[l4+1] other than (0,0), (3,0..4) -> NONE.
+             A source p[l3+12:l3+16] that is neither loopback nor global unicast -> MCAST
+             (pktRxErrMulticastB, icmp.go:433-436; the responder's predicate).  l4 != l3 + 20 -> HOST:
+             gopacket's IPv4.DecodeFromBytes over the 20-byte slice fails for IHL > 5 (layers/
+             ip4.go:336-343, pktRxErrTooShort), which stays with Go.  CLIENT_NO_PLUGIN, or a client
+             without the icmp plugin in the client info table (the classifier gives this callback
+             CLIENT whatever the client's plugins are) -> NO_CLIENT (GetIcmpClientByMac
+             icmp.go:349-351, :384-386: after IsUnicastToMe the client of the destination MAC is
+             rec.client_id).  Echo reply: len - (l4 + 8) < 16 -> HOST (icmp.go:182-185),
+             else REPLY with identifier p[l4+4:l4+6], sequence number p[l4+6:l4+8], magic
+             p[l4+8:l4+16] and timestamp p[l4+16:l4+24], all big-endian.  Unreachable: len < l4 + 36
+             -> HOST (icmp.go:378), else UNREACH with the nested identifier p[l4+32:l4+34].  The
+             client is rec.client_id.
+     icmpv6  type, code other than (129,0), (1,0..6), or a lookup other than NS_LEVEL -> NONE.  Echo
+             reply: len - l4 < 24 -> HOST (ipv6.go:389); unreachable: len - l4 < 72 -> HOST (:445).
+             The client is CLookupByMac(p[0:6]) in rec.ns_id (GetIcmpClientByMac ipv6.go:559-573),
+             probed in the MAC table; none, or one without the ipv6 plugin -> NO_CLIENT
+             (pktRxNoClientUnhandled :397-399, :453-455).  The reply's fields sit at the same offsets
+             from l4 as in icmp; the unreachable's identifier is p[l4+52:l4+54].
+   A REPLY (Ping.HandleEchoReply ping.go:246-295) whose magic is not 0xc15c0c15c0be5be5 (:198) is
+   malformed; else, with ts the timestamp as int64, it is accepted iff now - 5e9 <= ts <= now
+   (signed: Go's latency < 0 || latency > 5 s with Time.Sub saturating), with latency now - ts;
+   otherwise it has a bad latency.
+   An event folds all frames of one key {ns_id, client_id, family, ident}; MCAST and NO_CLIENT
+   frames fold into the Namespace-level key {ns_id, 0xffffffff, family, 0}.  lat_min_tail is the
+   minimum over the accepted replies behind the last accepted reply with latency 0 (over all of
+   them if none has latency 0; 0 if that reply is the last one): what ping.go:290-293 leaves, where
+   a zero minimum is replaced by the next latency.  Events are written in ascending `last`, so the
+   output is fully determined.  d_info (u64[EMURX_PNG_INFO_WORDS]) = {events written, distinct
+   keys, overflow (0 or 1), frames with outcome 1..5}; overflow is distinct keys > ev_cap and
+   nothing else: then d_info[0] is 0 and nothing is written to d_ev, while d_outcome and
+   d_info[1..7] stay valid.  Nothing is ever written at or past d_ev[ev_cap].  A frame with outcome
+   1..4 needs no Go handler when the batch did not overflow: INTEGRATION.md has the replay loop.
+   fams == 0 or a bit above EMURX_PNGK_ALL, now_unix_ns >= 2^63, ev_cap == 0 or ev_cap >
+   emurx_ping_max_events(h), a NULL d_ev or d_info, with n > 0 a NULL d_frames, d_desc or d_rec,
+   and a capturing stream are EMURX_EINVAL; n > cfg.max_frames is EMURX_ENOMEM; a host-only handle
+   EMURX_EDEVICE.  d_rec 16-byte aligned, d_desc, d_ev and d_info 8-byte; d_outcome [n] may be
+   NULL.  n < EMURX_TX_ZMQ_MAX_FRAMES; n == 0 writes a zero d_info.  Five launches on `stream`
+   (decide, fold, mark, scan + the ordered pass, emit), no host synchronisation and no allocation
+   (the scratch, its own, is sized at emurx_open from max_frames and every call leaves it as it
+   found it), behind the table shipment emurx_classify_dev describes; calls on different streams
+   of one handle share the scratch, so they must not overlap.  emurx_ping_max_events(h) is
+   emurx_learn_max_events(h). */
+typedef struct emurx_ping_ev {       /* 80 bytes */
+    uint32_t ns_id, client_id;       /* client_id 0xffffffff: Namespace-level event */
+    uint16_t ident; uint8_t family /* 4 | 6 */, flags /* bit 0: an accepted latency was 0 */;
+    uint32_t first, last;            /* lowest / highest rx frame index folded */
+    uint32_t n_reply, n_unreach;     /* REPLY / UNREACH frames */
+    uint32_t n_malformed, n_bad_latency, n_ok;   /* partition of n_reply */
+    uint32_t n_succ;                 /* accepted replies whose predecessor (previous accepted
+                                        reply of this key in rx order) has seq - 1 mod 2^16 */
+    uint16_t seq_first, seq_last;    /* seq of the first / last accepted reply */
+    uint64_t lat_sum, lat_min_tail, lat_max;
+    uint32_t n_no_client, n_mcast;   /* Namespace-level events only */
+} emurx_ping_ev;
+enum emurx_png {            /* per-frame outcome, d_outcome[i] */
+    EMURX_PNG_NONE = 0,       /* not this call's frame */
+    EMURX_PNG_REPLY = 1, EMURX_PNG_UNREACH = 2,
+    EMURX_PNG_NO_CLIENT = 3,  /* pktRxNoClientUnhandled */
+    EMURX_PNG_MCAST = 4,      /* pktRxErrMulticastB */
+    EMURX_PNG_HOST = 5        /* the Go handler must decide */
+};
+#define EMURX_PNGK_V4 1u
+#define EMURX_PNGK_V6 2u
+#define EMURX_PNGK_ALL 3u
+#define EMURX_PNG_INFO_WORDS 8
+#define EMURX_PING_MAGIC 0xc15c0c15c0be5be5ull   /* ping.go:198 */
+#define EMURX_PING_TIMEOUT_NS 5000000000ull      /* DefaultPingTimeout, ping.go:267 */
+uint32_t emurx_ping_max_events(const emurx_t* h);
+int emurx_ping_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                   const emurx_rec* d_rec, uint32_t n, uint32_t fams, uint64_t now_unix_ns,
+                   emurx_ping_ev* d_ev, uint32_t ev_cap,
+                   uint8_t* d_outcome, uint64_t* d_info, void* stream);
+
 /* ---- the device answers on an ingest slot ---------------------------------------------------
    The batched ingest keeps a batch's frames, descriptors and records private to its slot, so a
    caller without device memory cannot hand them to the four calls above.  With answers on, a
@@ -1023,6 +1120,35 @@ int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out);
    least 54 bytes (l4 + 20 <= len with l4 >= 34).  emurx_ingest_set_answers keeps rejecting 16. */
 int emurx_ingest_set_answers_ts(emurx_t* h, uint32_t slot, uint32_t kinds);
 int emurx_ingest_set_time(emurx_t* h, uint32_t slot, uint32_t ip_time_ms);
+/* The ping fold on a slot.  emurx_ingest_set_ping(h, slot, fams) holds for the slot's later
+   submits; fams: EMURX_PNGK_* bits, 0 = off (the default).  It needs answers on for the slot, with
+   any kinds (else EMURX_EINVAL), and turning answers off turns it off.  The stage runs behind
+   nsstat in the slot's chain: emurx_ping_dev(fams) over the slot's frames, descriptors and records
+   with ev_cap = emurx_ping_max_events(h), so it cannot overflow, and the now_unix_ns that
+   emurx_ingest_set_now stored when the batch was submitted (each submit takes the value stored at
+   that moment, so two slots in flight carry their own; a host store, no device work, default 0;
+   2^63 and above are EMURX_EINVAL).  Then a launch of its own reads the stage's counts on the
+   device and writes the info words, the outcome array and the events produced, and no more, into
+   pinned memory the slot owns.  The first call with fams != 0 allocates everything for
+   cfg.max_frames and cfg.max_bytes (a folded frame is at least 42 bytes long, so a batch has at
+   most max_bytes / 42 events): no submit allocates or synchronises for it.  A slot with a batch
+   in flight, slot >= EMURX_INGEST_SLOTS or a bit above EMURX_PNGK_ALL are EMURX_EINVAL; a host-only
+   handle EMURX_EDEVICE.  emurx_ingest_ping(h, slot, &out), after the emurx_ingest_wait of that
+   batch, points `out` at library-owned memory, valid until the slot's next submit; outcome and the
+   events' first / last are in res.rec's numbering, also when messages fell short.  It returns
+   EMURX_ENOENT when the slot's last batch ran without ping, EMURX_EINVAL before any wait or with a
+   batch in flight.  The stage's scratch is the handle's: like the other stages', a caller's own
+   emurx_ping_dev must not overlap a slot's batch that has ping on.  emurx_answers, and everything
+   emurx_ingest_answers returns, are the same with ping on or off. */
+typedef struct emurx_ping_out {
+    const emurx_ping_ev* ev;      /* [n_ev] ascending `last` */
+    uint32_t n_ev;
+    const uint8_t* outcome;       /* [n_frames] enum emurx_png */
+    uint64_t info[EMURX_PNG_INFO_WORDS];
+} emurx_ping_out;
+int emurx_ingest_set_ping(emurx_t* h, uint32_t slot, uint32_t fams);
+int emurx_ingest_set_now(emurx_t* h, uint32_t slot, uint64_t now_unix_ns);
+int emurx_ingest_ping(emurx_t* h, uint32_t slot, emurx_ping_out* out);
 
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);

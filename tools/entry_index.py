@@ -58,6 +58,10 @@ GROUPS = [
     ("Device handler counters", ["emurx_nsstat_dev", "emurx_nsstat_ts_dev", "emurx_nsstat_max_events"],
      "the counters of `HandleRxArpPacket` `arp/arp.go:904-946`, `HandleRxIcmpPacket` `icmp/icmp.go:396-462`, "
      "`HandleRxIpv6Packet` `ipv6/ipv6.go:465-539`, `HandleRxIpv6NdPacket` `ipv6/nd.go:1546-1776`"),
+    ("Device ping fold", ["emurx_ping_dev", "emurx_ping_max_events", "emurx_ingest_set_ping", "emurx_ingest_set_now",
+                          "emurx_ingest_ping"],
+     "`HandleEchoReply` / `HandleDestinationUnreachable` `icmp/icmp.go:328-393`, `ipv6/ipv6.go:359-462`, "
+     "`Ping.HandleEchoReply` `ping/ping.go:246-304`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_uniform", "emurx_last_trim", "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

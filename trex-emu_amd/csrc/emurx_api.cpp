@@ -136,8 +136,20 @@ struct IngestSlot {
     View<uint32_t> h_src;
     View<emurx_learn_ev> h_lev;
     View<emurx_nsstat_ev> h_nsev;
+    // the ping stage (emurx_ingest_set_ping), behind nsstat in the chain: its outputs, sized once
+    uint32_t png_fams = 0, png_batch = 0;  // the setting for later submits; the batch in flight / last waited for
+    uint64_t png_now = 0;                  // emurx_ingest_set_now: now_unix_ns of the slot's next submits
+    uint32_t png_ev_cap = 0;               // events the pinned block holds
+    DevBuf<emurx_ping_ev> d_pev;
+    DevBuf<uint64_t> d_pinfo;
+    DevBuf<uint8_t> d_pngo;
+    PinBuf<uint8_t> h_png;                 // the pinned block (k_png_out writes it)
+    View<uint64_t> h_pinfo;
+    View<uint8_t> h_pngo;
+    View<emurx_ping_ev> h_pev;
     void release() {
         if (st) (void)hipStreamSynchronize(st);
+        d_pev.release(); d_pinfo.release(); d_pngo.release(); h_png.release();
         d_rsp_out.release(); d_tx.release(); d_rsp_desc.release(); d_rsp_src.release(); d_tx_off.release();
         d_ainfo.release(); d_lev.release(); d_nsev.release(); h_ans.release();
         d_qseg.release(); d_tcnt.release(); d_ticket.release(); d_hsmall.release(); h_done.release();
@@ -223,6 +235,10 @@ struct emurx_ctx {
     // and max_ns: its accumulator rows and flags are zero between calls, cleared like the learning set
     DevBuf<uint8_t> d_nss;
     bool nss_dirty = false;
+    // the ping fold's scratch (emurx_ping_dev), sized at emurx_open from max_frames: its accumulator
+    // rows and its set are zero between calls, cleared like the learning set
+    DevBuf<uint8_t> d_png;
+    bool png_dirty = false;
     // the answer stages of ingest slots (emurx_ingest_set_answers) share the four scratches above:
     // each stage waits for the previous one's event and records its own
     hipEvent_t ans_ev = nullptr;
@@ -719,6 +735,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
         s.seq = (s.seq + 1) & 0x7fffffffu;  // bit 31 of the completion word: the batch was degraded
         s.small = true;
         s.ans_batch = 0;
+        s.png_batch = 0;
         s.pending = true;
         s.nmsg = nmsg;
         s.slots = n;
@@ -747,6 +764,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     if (!ok) return EMURX_EDEVICE;
     s.small = false;
     s.ans_batch = kinds;
+    s.png_batch = kinds ? s.png_fams : 0;
     s.pending = true;
     s.nmsg = nmsg;
     s.slots = n;
@@ -778,8 +796,8 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
     if (rc) return rc;
     s.pending = false;
     s.waited = true;
-    const uint32_t ans = s.ans_batch;
-    s.ans_batch = 0;  // set again below, once the answers are checked and renumbered
+    const uint32_t ans = s.ans_batch, png = s.png_batch;
+    s.ans_batch = s.png_batch = 0;  // set again below, once the answers are checked and renumbered
     if (!(s.small && h->ingest_spin && spin_done(s.h_done.p, s.seq)) && !EMURX_HIP_OK(hipEventSynchronize(s.done)))
         return EMURX_EDEVICE;
     memset(res, 0, sizeof(*res));
@@ -806,6 +824,7 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
                 memmove(s.h_desc.p + c, s.h_desc.p + base[m], (size_t)f * sizeof(emurx_desc));
                 for (View<uint8_t>* v : {&s.h_rspo, &s.h_lrno, &s.h_donef})
                     if (ans) memmove(v->p + c, v->p + base[m], f);
+                if (png) memmove(s.h_pngo.p + c, s.h_pngo.p + base[m], f);
             }
             for (uint32_t k = 0; k < f; ++k) s.remap[base[m] + k] = c + k;
             c += f;
@@ -824,16 +843,24 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
                        ntx = hd[EMURX_ANS_HEAD_TX], txb = hd[EMURX_ANS_HEAD_TX + 1];
         if (nrep > s.ans_r_cap || ntx > s.ans_r_cap || txb > s.ans_tx_cap || nlrn > s.ans_ev_cap || nns > s.ans_ns_cap)
             return EMURX_EDEVICE;
-        if (nf < s.slots) {  // slot numbers -> the closed numbering (monotone: ascending `last` survives)
-            auto closed = [&](uint32_t& j) {
-                if (j >= s.slots || s.remap[j] == EMURX_ID_NONE) return false;
-                j = s.remap[j];
-                return true;
-            };
+        // slot numbers -> the closed numbering (monotone: ascending `last` survives)
+        auto closed = [&](uint32_t& j) {
+            if (j >= s.slots || s.remap[j] == EMURX_ID_NONE) return false;
+            j = s.remap[j];
+            return true;
+        };
+        if (nf < s.slots) {
             for (uint64_t k = 0; k < nrep; ++k)
                 if (!closed(s.h_src.p[k])) return EMURX_EDEVICE;
             for (uint64_t k = 0; k < nlrn; ++k)
                 if (!closed(s.h_lev.p[k].first) || !closed(s.h_lev.p[k].last)) return EMURX_EDEVICE;
+        }
+        if (png) {
+            const uint64_t npng = s.h_pinfo.p[0];
+            if (npng > s.png_ev_cap) return EMURX_EDEVICE;
+            for (uint64_t k = 0; k < npng && nf < s.slots; ++k)
+                if (!closed(s.h_pev.p[k].first) || !closed(s.h_pev.p[k].last)) return EMURX_EDEVICE;
+            s.png_batch = png;
         }
         s.ans_batch = ans;
     }
@@ -939,6 +966,11 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
         emurx_close(h);
         return EMURX_ENOMEM;
     }
+    if (h->d_png.alloc(emurx_png_scratch_bytes(cfg->max_frames)) ||
+        emurx_png_scratch_clear(h->d_png.p, cfg->max_frames, h->stream) || !EMURX_HIP_OK(hipStreamSynchronize(h->stream))) {
+        emurx_close(h);
+        return EMURX_ENOMEM;
+    }
     emurx_t::RouteScratch* rs = nullptr;
     if ((rc = ship_tables(h, h->stream)) || (rc = route_scratch(h, cfg->max_frames, h->stream, &rs)) == EMURX_ENOMEM) {
         emurx_close(h);
@@ -975,6 +1007,7 @@ void emurx_close(emurx_t* h) {
     h->d_rsp.release();
     h->d_lrn.release();
     h->d_nss.release();
+    h->d_png.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
     if (h->ans_ev) (void)hipEventDestroy(h->ans_ev);
@@ -1662,6 +1695,35 @@ int emurx_nsstat_ts_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d
                         d_done, d_info, stream);
 }
 
+uint32_t emurx_ping_max_events(const emurx_t* h) { return emurx_learn_max_events(h); }
+
+int emurx_ping_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec, uint32_t n,
+                   uint32_t fams, uint64_t now_unix_ns, emurx_ping_ev* d_ev, uint32_t ev_cap, uint8_t* d_outcome,
+                   uint64_t* d_info, void* stream) {
+    if (!h || !d_info || !d_ev || (n && (!d_frames || !d_desc || !d_rec))) return EMURX_EINVAL;
+    if (fams == 0 || (fams & ~EMURX_PNGK_ALL) || (now_unix_ns >> 63)) return EMURX_EINVAL;
+    if (ev_cap == 0 || ev_cap > emurx_ping_max_events(h)) return EMURX_EINVAL;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ev & 7) ||
+        ((uintptr_t)d_info & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;  // the scratch is sized at emurx_open
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // an ICMPv6 frame's client is looked up in the MAC table: behind the shipment of pending edits, like a classify
+    if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
+    if (h->png_dirty) {
+        if (emurx_png_scratch_clear(h->d_png.p, h->cfg.max_frames, st)) return EMURX_EDEVICE;
+        h->png_dirty = false;
+    }
+    if (emurx_launch_ping(d_frames, d_desc, d_rec, n, fams, now_unix_ns, h->tables(), d_ev, ev_cap, d_outcome, d_info,
+                          h->d_png.p, h->cfg.max_frames, st)) {
+        h->png_dirty = true;
+        return EMURX_EDEVICE;
+    }
+    return EMURX_OK;
+}
+
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {
     if (!key || n_parts == 0) return 0;
     return emurx_owner(emurx_tk_hash(le32(key), le32(key + 4), le32(key + 8)), n_parts);
@@ -1758,9 +1820,17 @@ int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
     if ((rc = emurx_nsstat_ts_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, s.d_rspo.p, s.d_lrno.p, s.d_nsev.p,
                                   emurx_nsstat_max_events(h), s.d_donef.p, nss_info, st)))
         return rc;
+    // the ping stage, with the slot's own time of day as a launch argument
+    const uint32_t fams = s.png_fams;
+    if (fams && (rc = emurx_ping_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, fams, s.png_now, s.d_pev.p, emurx_ping_max_events(h),
+                                     s.d_pngo.p, s.d_pinfo.p, st)))
+        return rc;
     // the shared scratch is free again: the next slot's stage may start while this one copies out
     if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
     h->ans_recorded = true;
+    if (fams && emurx_launch_ping_out(s.d_pinfo.p, s.d_pev.p, s.d_pngo.p, n, s.png_ev_cap, reinterpret_cast<uint8_t*>(s.h_pinfo.p),
+                                      reinterpret_cast<uint8_t*>(s.h_pev.p), s.h_pngo.p, st))
+        return EMURX_EDEVICE;
     const emurx_ans_out a{reinterpret_cast<const unsigned long long*>(rsp_info),
                           reinterpret_cast<const unsigned long long*>(tx_info),
                           reinterpret_cast<const unsigned long long*>(lrn_info),
@@ -1791,6 +1861,7 @@ int set_answers(emurx_t* h, uint32_t slot, uint32_t kinds, uint32_t allowed) {
     if (rc) return rc;
     IngestSlot& s = h->ing[slot];
     if (s.pending) return EMURX_EINVAL;
+    if (!kinds) s.png_fams = 0;  // no chain, no ping stage
     if (!kinds || s.h_ans.p) {  // off, or sized by an earlier call
         s.ans_kinds = kinds;
         return EMURX_OK;
@@ -1846,6 +1917,59 @@ int emurx_ingest_set_time(emurx_t* h, uint32_t slot, uint32_t ip_time_ms) {
     IngestSlot& s = h->ing[slot];
     if (s.pending) return EMURX_EINVAL;
     s.ans_time = ip_time_ms;
+    return EMURX_OK;
+}
+
+int emurx_ingest_set_ping(emurx_t* h, uint32_t slot, uint32_t fams) {
+    if (!h || slot >= EMURX_INGEST_SLOTS || (fams & ~EMURX_PNGK_ALL)) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    IngestSlot& s = h->ing[slot];
+    if (s.pending || (fams && !s.ans_kinds)) return EMURX_EINVAL;  // the stage is part of the answer chain
+    if (!fams || s.h_png.p) {  // off, or sized by an earlier call
+        s.png_fams = fams;
+        return EMURX_OK;
+    }
+    // everything the stage needs, now: no submit allocates or synchronises for it.  A folded frame
+    // is at least 42 bytes long (l3 >= 14, 20 bytes of IPv4 header and 8 of ICMP, or more), so a
+    // batch has at most max_bytes / 42 events: the answer block's bound.
+    const uint32_t mf = std::min<uint32_t>(h->cfg.max_frames, EMURX_TX_ZMQ_MAX_FRAMES - 1);
+    const uint32_t cap = answer_caps(h).ev;
+    if (s.d_pev.alloc((size_t)emurx_ping_max_events(h) + 1) || s.d_pinfo.alloc(EMURX_PNG_INFO_WORDS) || s.d_pngo.alloc((size_t)mf + 16))
+        return EMURX_ENOMEM;
+    auto carve = [&](uint8_t* block) {
+        emurx_carver k(block);
+        s.h_pinfo.p = k.take<uint64_t>(EMURX_PNG_INFO_WORDS);
+        s.h_pngo.p = k.take<uint8_t>((size_t)mf + 16);
+        s.h_pev.p = k.take<emurx_ping_ev>(cap);
+        return k.bytes();
+    };
+    if (s.h_png.alloc(carve(nullptr))) return EMURX_ENOMEM;
+    carve(s.h_png.p);
+    memset(s.h_pinfo.p, 0, EMURX_PNG_INFO_WORDS * sizeof(uint64_t));
+    s.png_ev_cap = cap;
+    s.png_fams = fams;
+    return EMURX_OK;
+}
+
+int emurx_ingest_set_now(emurx_t* h, uint32_t slot, uint64_t now_unix_ns) {
+    if (!h || slot >= EMURX_INGEST_SLOTS || (now_unix_ns >> 63)) return EMURX_EINVAL;
+    IngestSlot& s = h->ing[slot];
+    if (s.pending) return EMURX_EINVAL;
+    s.png_now = now_unix_ns;
+    return EMURX_OK;
+}
+
+int emurx_ingest_ping(emurx_t* h, uint32_t slot, emurx_ping_out* out) {
+    if (!h || !out || slot >= EMURX_INGEST_SLOTS) return EMURX_EINVAL;
+    const IngestSlot& s = h->ing[slot];
+    if (s.pending || !s.waited) return EMURX_EINVAL;
+    if (!s.png_batch) return EMURX_ENOENT;
+    memset(out, 0, sizeof(*out));
+    out->ev = s.h_pev.p;
+    out->n_ev = (uint32_t)s.h_pinfo.p[0];
+    out->outcome = s.h_pngo.p;
+    memcpy(out->info, s.h_pinfo.p, sizeof(out->info));
     return EMURX_OK;
 }
 

@@ -227,6 +227,18 @@ int emurx_launch_nsstat(const uint8_t* frames, const emurx_desc* desc, const emu
                         const uint8_t* rsp_outcome, const uint8_t* lrn_outcome, emurx_nsstat_ev* ev, uint32_t ev_cap,
                         uint8_t* done, uint64_t* info, void* scratch, uint32_t max_frames, uint32_t max_ns, hipStream_t st);
 
+// The ping fold (emurx_ping.hip): see emurx_ping_dev.  scratch: emurx_png_scratch_bytes(max_frames)
+// bytes, whose accumulator rows and owner words emurx_png_scratch_clear zeroes before the first
+// call; every call leaves them zero.  n <= max_frames.  Five launches.
+size_t emurx_png_scratch_bytes(uint32_t max_frames);
+int emurx_png_scratch_clear(void* scratch, uint32_t max_frames, hipStream_t st);
+// a slot's ping stage to its pinned block (k_png_out): info, n outcome bytes, min(info[0], ev_cap) events
+int emurx_launch_ping_out(const uint64_t* info, const emurx_ping_ev* ev, const uint8_t* outcome, uint32_t n, uint32_t ev_cap,
+                          uint8_t* h_info, uint8_t* h_ev, uint8_t* h_outcome, hipStream_t st);
+int emurx_launch_ping(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, uint32_t n, uint32_t fams,
+                      uint64_t now_unix_ns, const emurx_dev_tables& T, emurx_ping_ev* ev, uint32_t ev_cap, uint8_t* outcome,
+                      uint64_t* info, void* scratch, uint32_t max_frames, hipStream_t st);
+
 // Tx ZMQ framing (emurx_txzmq.hip): see emurx_tx_zmq_dev.  scratch: emurx_txz_scratch_bytes(n).
 size_t emurx_txz_scratch_bytes(uint32_t n);
 // variant: the write kernel's image (EMURX_TXZ_*, emurx_tx_zmq_dev's feedback choice); feedback:

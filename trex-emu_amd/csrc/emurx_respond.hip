@@ -58,15 +58,6 @@ __device__ __forceinline__ uint32_t rsp_update_csum(uint32_t cs, uint32_t oldv, 
     return ~s & 0xffffu;
 }
 
-// Go 1.18 net.IP.IsLoopback || IsGlobalUnicast for an IPv4 address (bytes b0.b1.x.x, ip = the
-// four wire bytes little-endian): not 0.0.0.0, 255.255.255.255, 224.0.0.0/4, 169.254.0.0/16.
-// The rule is Go's standard library (net/ip.go), not the reference tree: as unpinned by the
-// reference's own tests as ip6_local_or_global (emurx_parse.h) is.
-__device__ __forceinline__ bool rsp_ip4_src_ok(uint32_t ip) {
-    const uint32_t b0 = ip & 0xff, b1 = (ip >> 8) & 0xff;
-    return !(ip == 0 || ip == 0xffffffffu || (b0 & 0xf0) == 0xe0 || (b0 == 169 && b1 == 254));
-}
-
 // the client of (record's tunnel key, ip) in the IPv4 table, with its MAC (CLookupByIPv4)
 __device__ __forceinline__ IpHit rsp_probe_ip4(const emurx_dev_tables& T, uint32_t ns, uint32_t vport, uint32_t v0,
                                                uint32_t v1, uint32_t ip) {

@@ -1,5 +1,5 @@
-// emurx_rsp_dev.h — device functions the responder (emurx_respond.hip) and the cache-learning
-// fold (emurx_learn.hip) share: unaligned frame spans, the checks of a neighbour solicitation
+// emurx_rsp_dev.h — device functions the responder (emurx_respond.hip), the cache-learning fold
+// (emurx_learn.hip) and the ping fold (emurx_ping.hip) share: the IPv4 source predicate, unaligned frame spans, the checks of a neighbour solicitation
 // (plugins/ipv6/nd.go:1550-1609) and the lookup of the client that owns an ND target.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +11,15 @@ namespace emurx {
 
 __device__ __forceinline__ uint32_t rsp_le32(const uint8_t* p) {  // any alignment
     return gld1(p) | gld1(p + 1) << 8 | gld1(p + 2) << 16 | gld1(p + 3) << 24;
+}
+
+// Go 1.18 net.IP.IsLoopback || IsGlobalUnicast for an IPv4 address (bytes b0.b1.x.x, ip = the
+// four wire bytes little-endian): not 0.0.0.0, 255.255.255.255, 224.0.0.0/4, 169.254.0.0/16.
+// The rule is Go's standard library (net/ip.go), not the reference tree: as unpinned by the
+// reference's own tests as ip6_local_or_global (emurx_parse.h) is.
+__device__ __forceinline__ bool rsp_ip4_src_ok(uint32_t ip) {
+    const uint32_t b0 = ip & 0xff, b1 = (ip >> 8) & 0xff;
+    return !(ip == 0 || ip == 0xffffffffu || (b0 & 0xf0) == 0xe0 || (b0 == 169 && b1 == 254));
 }
 
 // E[s .. s + 16) of the frame E = [F, F + flen), s of either sign, as four little-endian words:

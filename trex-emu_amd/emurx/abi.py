@@ -152,6 +152,20 @@ NSC_GO_TS = NSC_GO + [("icmp", ("pktRxErrTooShort",))]
 # emurx_nsstat_ev: one event per Namespace with a frame whose handler is not needed
 NSSTAT_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("frames", "<u4"), ("cnt", "<u4", NSC_WORDS)])
 assert NSSTAT_EV_DTYPE.itemsize == 96
+# enum emurx_png: the per-frame outcome of emurx_ping_dev
+PNG_NONE, PNG_REPLY, PNG_UNREACH, PNG_NO_CLIENT, PNG_MCAST, PNG_HOST = range(6)
+# EMURX_PNGK_*: the families emurx_ping_dev is asked to fold; its d_info has PNG_INFO_WORDS words
+PNGK_V4, PNGK_V6, PNGK_ALL = 1, 2, 3
+PNG_INFO_WORDS = 8
+PING_MAGIC, PING_TIMEOUT_NS = 0xC15C0C15C0BE5BE5, 5_000_000_000  # ping.go:198, :267
+PING_NS_LEVEL = 0xFFFFFFFF  # client_id of a Namespace-level event
+# emurx_ping_ev: one event per {ns_id, client_id, family, ident} of a batch
+PING_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("client_id", "<u4"), ("ident", "<u2"), ("family", "u1"), ("flags", "u1"),
+                          ("first", "<u4"), ("last", "<u4"), ("n_reply", "<u4"), ("n_unreach", "<u4"),
+                          ("n_malformed", "<u4"), ("n_bad_latency", "<u4"), ("n_ok", "<u4"), ("n_succ", "<u4"),
+                          ("seq_first", "<u2"), ("seq_last", "<u2"), ("lat_sum", "<u8"), ("lat_min_tail", "<u8"),
+                          ("lat_max", "<u8"), ("n_no_client", "<u4"), ("n_mcast", "<u4")])
+assert PING_EV_DTYPE.itemsize == 80
 FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xFFFFFFF0, 0xFFFFFFF1,
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
@@ -196,6 +210,11 @@ class Answers(C.Structure):
                 ("lrn_outcome", C.c_void_p), ("done", C.c_void_p), ("learn_ev", C.c_void_p), ("n_learn", C.c_uint32),
                 ("ns_ev", C.c_void_p), ("n_ns", C.c_uint32), ("rsp_info", C.c_uint64 * RSP_INFO_WORDS),
                 ("lrn_info", C.c_uint64 * LRN_INFO_WORDS), ("nss_info", C.c_uint64 * NSS_INFO_WORDS)]
+
+
+class PingOut(C.Structure):
+    """emurx_ping_out: a slot's ping fold (emurx_ingest_ping); pointers into library memory."""
+    _fields_ = [("ev", C.c_void_p), ("n_ev", C.c_uint32), ("outcome", C.c_void_p), ("info", C.c_uint64 * PNG_INFO_WORDS)]
 
 
 class DevOut(C.Structure):
@@ -289,6 +308,11 @@ SIGNATURES = [
     ("emurx_nsstat_max_events", C.c_uint32, [_P]),
     ("emurx_nsstat_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     ("emurx_nsstat_ts_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_ping_max_events", C.c_uint32, [_P]),
+    ("emurx_ping_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint64, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_ingest_set_ping", C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    ("emurx_ingest_set_now", C.c_int, [_P, C.c_uint32, C.c_uint64]),
+    ("emurx_ingest_ping", C.c_int, [_P, C.c_uint32, C.POINTER(PingOut)]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -309,7 +333,8 @@ SIGNATURES = [
 # measurement observables that an older library given through EMURX_LIB (A/B runs of one
 # bench.py against two builds) may lack; calling one it lacks is an AttributeError
 OPTIONAL = {"emurx_last_uniform", "emurx_last_trim", "emurx_respond_ts_dev", "emurx_nsstat_ts_dev",
-            "emurx_ingest_set_answers_ts", "emurx_ingest_set_time"}
+            "emurx_ingest_set_answers_ts", "emurx_ingest_set_time", "emurx_ping_max_events", "emurx_ping_dev",
+            "emurx_ingest_set_ping", "emurx_ingest_set_now", "emurx_ingest_ping"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
 TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 
@@ -348,7 +373,7 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
-           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()

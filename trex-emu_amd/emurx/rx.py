@@ -292,6 +292,30 @@ class RxPath:
                     nss_info=np.array(a.nss_info, np.uint64), n_replies=int(a.n_replies), n_tx_msgs=int(a.n_tx_msgs),
                     tx_bytes=int(a.tx_bytes))
 
+    def ingest_set_ping(self, slot: int, fams: int) -> None:
+        """Run the ping fold behind nsstat in the slot's answer chain on its later batches: fams
+        abi.PNGK_* bits, 0 turns it off; answers must be on (include/emu_rx.h emurx_ingest_set_ping)."""
+        abi.check(self.lib.emurx_ingest_set_ping(self.h, slot, fams), "ingest_set_ping")
+
+    def ingest_set_now(self, slot: int, now_unix_ns: int) -> None:
+        """The time.Now().UnixNano() that the slot's next submits pass to the ping fold
+        (include/emu_rx.h emurx_ingest_set_now)."""
+        abi.check(self.lib.emurx_ingest_set_now(self.h, slot, now_unix_ns), "ingest_set_now")
+
+    def ingest_ping(self, slot: int, n_frames: int) -> dict:
+        """The ping fold of the slot's batch, after its ingest_wait (n_frames: that result's n), as
+        numpy copies: ev (abi.PING_EV_DTYPE, ascending `last`), outcome u8 [n_frames], info."""
+        a = abi.PingOut()
+        abi.check(self.lib.emurx_ingest_ping(self.h, slot, C.byref(a)), "ingest_ping")
+
+        def copy(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            b = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dt).itemsize,))
+            return b.view(dt).copy()
+        return dict(ev=copy(a.ev, a.n_ev, abi.PING_EV_DTYPE), outcome=copy(a.outcome, n_frames, np.uint8),
+                    info=np.array(a.info, np.uint64))
+
     # ---- tx-side checksum generation ------------------------------------------------------
     def tx_checksum_dev(self, frames, desc, n: int, status=None, stream=None):
         """Rewrite the checksums selected by each TX_DESC_DTYPE descriptor, in place on the
@@ -374,6 +398,22 @@ class RxPath:
         return abi.check(self.lib.emurx_nsstat_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, kinds,
                                                    _addr(rsp_outcome), _addr(lrn_outcome), _addr(ev), ev_cap, _addr(done),
                                                    _addr(info), _stream(stream)), "nsstat_dev")
+
+    def ping_max_events(self) -> int:
+        """The largest ev_cap ping_dev takes (that of learn_dev)."""
+        return int(self.lib.emurx_ping_max_events(self.h))
+
+    def ping_dev(self, frames, desc, rec, n: int, now_unix_ns: int, ev, ev_cap: int, outcome, info,
+                 fams: int = abi.PNGK_ALL, stream=None):
+        """The echo replies and destination-unreachable messages of a classified batch folded on the
+        device into one event per {ns_id, client_id, family, ident} (include/emu_rx.h
+        emurx_ping_dev): now_unix_ns is the batch's one time.Now().UnixNano(); ev abi.PING_EV_DTYPE
+        [ev_cap], written in ascending `last`; outcome u8 [n] (abi.PNG_*, or None); info
+        u64[abi.PNG_INFO_WORDS] {events written, distinct keys, overflow, frames per outcome 1..5}.
+        On overflow (distinct keys > ev_cap) no event is written."""
+        return abi.check(self.lib.emurx_ping_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, fams, now_unix_ns,
+                                                 _addr(ev), ev_cap, _addr(outcome), _addr(info), _stream(stream)),
+                         "ping_dev")
 
     # ---- Namespace-partitioned exchange ---------------------------------------------------
     def classify_route_dev(self, frames, desc, n: int, rec, qlist, qcap: int, tile_cnt, hist, n_parts: int,
