@@ -1055,6 +1055,82 @@ int emurx_ping_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc
                    emurx_ping_ev* d_ev, uint32_t ev_cap,
                    uint8_t* d_outcome, uint64_t* d_info, void* stream);
 
+/* ---- TCP / UDP frames the transport plugin refuses, folded per client --------------------------
+   A tcp / udp frame reaches HandleRxTransPacket (plugins/transport/plugin_transport.go:74-128),
+   which finds the Namespace plugin, the client and its plugin, then the client's TransportCtx, whose
+   handleRxPacket (client_ctx.go:912-969) probes the flow table and, on a miss, calls
+   handleRxTcpNewFlow / handleRxUdpNewFlow (:829-906).  The classifier takes that decision on the
+   device (emurx_dev_out.flow).  For a frame that reaches no socket all the handler does is bump two
+   to four ftStats counters (client_ctx.go:158-197) or return PARSER_ERR: pure counts, so nothing
+   depends on frame order and emurx_ftstat_dev folds them exactly, one event per client.
+   d_frames, d_desc, d_rec, d_flow: as ONE emurx_classify_dev call on this handle wrote them
+   (out.flow non-NULL); records and flow words of emurx_lookup_dev on another GPU are out of scope.
+   A frame is a candidate if rec.status == EMURX_ST_OK, its descriptor is no hole and rec.proto is
+   EMURX_CB_TCP or EMURX_CB_UDP; every other frame gets EMURX_FT_NONE.  For a candidate, by lookup:
+     NO_NS, NS_NO_PLUGIN, NO_CLIENT, CLIENT_NO_PLUGIN -> EMURX_FT_ERR: the handler would only return
+             PARSER_ERR (-1, plugin_transport.go:82-128), which HandleRxPacket counts as errParser
+             (core/thread_ctx.go:365-372).
+     LK_NONE, NS_LEVEL -> NONE.  CLIENT with rec.client_id >= cfg.max_clients or rec.ns_id >=
+             cfg.max_ns -> NONE.
+     CLIENT  by d_flow[i]:
+             EMURX_FLOW_NO_CTX -> EMURX_FT_ERR (plugin_transport.go:75-78, returns -1).
+             EMURX_FLOW_NO_SYN with the tcp callback -> EMURX_FT_NO_SYN: ft_lookupv4 | ft_lookupv6
+             (client_ctx.go:927 / :951), ft_new_tcp (:837), ft_new_tcp_no_syn (:842); with the udp
+             callback -> NONE (the classifier never produces that combination).
+             EMURX_FLOW_NO_SERVER with the tcp callback -> EMURX_FT_NO_SRV_TCP: ft_lookup*,
+             ft_new_tcp (:837), ft_new_no_cb (:851); with the udp callback -> EMURX_FT_NO_SRV_UDP:
+             ft_lookup*, ft_new_udp (:878), ft_new_no_cb (:886).
+             A flow id, EMURX_FLOW_NEW, EMURX_FLOW_UNKNOWN and EMURX_FLOW_NONE -> NONE: the handler
+             runs and counts itself.
+   handleRxPacket returns 0 on the three folded paths (it ignores the new-flow functions' return
+   values, :936-942), so these frames add nothing to errParser.  The family is p[l3] >> 4 == 4, as
+   :918-920 and get_tuple read it: the only byte of the frame the fold reads, and only for outcomes
+   1..3; before that read l3 < 14 or l3 >= len gives NONE.  IPv6 sets EMURX_FT_V6 in the outcome
+   byte, which therefore states exactly which counters a frame contributed: outcome & 7 = 1 -> LOOKUP,
+   NEW_TCP, NEW_TCP_NO_SYN; 2 -> LOOKUP, NEW_TCP, NEW_NO_CB; 3 -> LOOKUP, NEW_UDP, NEW_NO_CB, where
+   LOOKUP is EMURX_FTC_LOOKUP_V6 with EMURX_FT_V6 and EMURX_FTC_LOOKUP_V4 without.
+   There is one event per client_id that has a frame with outcome 1..3 (ns_id: its last such
+   frame's record's); first / last are the lowest / highest rx frame index folded, frames their
+   number, cnt[EMURX_FTC_*] what to add to the client's ftStats (cnt[6] is zero).  Events are written
+   in ascending `last`, so the output is fully determined.  EMURX_FT_ERR frames make no event.
+   d_info (u64[EMURX_FT_INFO_WORDS]) = {events written, distinct clients, overflow (0 or 1), frames
+   NO_SYN, NO_SRV_TCP, NO_SRV_UDP, ERR, candidates left at NONE}; overflow is distinct clients >
+   ev_cap and nothing else: then d_info[0] is 0 and nothing is written to d_ev, while d_outcome and
+   d_info[1..7] stay valid.  Nothing is ever written at or past d_ev[ev_cap].  INTEGRATION.md has
+   the replay loop, the dispatch rule and the rule for frames emurx_recs_stale flags.
+   ev_cap == 0 or ev_cap > emurx_ftstat_max_events(h), a NULL d_ev or d_info, with n > 0 a NULL
+   d_frames, d_desc, d_rec or d_flow, and a capturing stream are EMURX_EINVAL; n > cfg.max_frames is
+   EMURX_ENOMEM; a host-only handle EMURX_EDEVICE.  d_rec 16-byte aligned, d_desc, d_ev and d_info
+   8-byte, d_flow 4-byte; d_outcome [n] may be NULL.  n < EMURX_TX_ZMQ_MAX_FRAMES; n == 0 writes a
+   zero d_info.  Four launches on `stream` (decide + fold, mark, scan, emit), no host synchronisation
+   and no allocation (the scratch, its own, is sized at emurx_open from max_frames and every call
+   leaves it as it found it), behind the table shipment emurx_classify_dev describes; calls on
+   different streams of one handle share the scratch, so they must not overlap.
+   emurx_ftstat_max_events(h) is min(cfg.max_frames, cfg.max_clients). */
+enum emurx_ft {             /* per-frame outcome, d_outcome[i] & 7 */
+    EMURX_FT_NONE = 0,        /* the transport handler runs (or the frame is none of its) */
+    EMURX_FT_NO_SYN = 1, EMURX_FT_NO_SRV_TCP = 2, EMURX_FT_NO_SRV_UDP = 3,
+    EMURX_FT_ERR = 4          /* the handler would return PARSER_ERR: errParser += 1 */
+};
+#define EMURX_FT_V6 0x08u   /* with outcome 1..3: the frame is IPv6 */
+enum emurx_ftc {            /* ftStats words of an event, client_ctx.go:158-197 */
+    EMURX_FTC_LOOKUP_V4 = 0, EMURX_FTC_LOOKUP_V6, EMURX_FTC_NEW_TCP, EMURX_FTC_NEW_TCP_NO_SYN,
+    EMURX_FTC_NEW_UDP, EMURX_FTC_NEW_NO_CB
+};
+#define EMURX_FTC_WORDS 7   /* word 6 is zero */
+#define EMURX_FT_INFO_WORDS 8
+typedef struct emurx_ft_ev {         /* 48 bytes */
+    uint32_t ns_id, client_id;
+    uint32_t first, last;            /* lowest / highest rx frame index folded */
+    uint32_t frames;                 /* frames folded */
+    uint32_t cnt[EMURX_FTC_WORDS];
+} emurx_ft_ev;
+uint32_t emurx_ftstat_max_events(const emurx_t* h);
+int emurx_ftstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc,
+                     const emurx_rec* d_rec, const uint32_t* d_flow, uint32_t n,
+                     emurx_ft_ev* d_ev, uint32_t ev_cap,
+                     uint8_t* d_outcome, uint64_t* d_info, void* stream);
+
 /* ---- the device answers on an ingest slot ---------------------------------------------------
    The batched ingest keeps a batch's frames, descriptors and records private to its slot, so a
    caller without device memory cannot hand them to the four calls above.  With answers on, a
@@ -1149,6 +1225,39 @@ typedef struct emurx_ping_out {
 int emurx_ingest_set_ping(emurx_t* h, uint32_t slot, uint32_t fams);
 int emurx_ingest_set_now(emurx_t* h, uint32_t slot, uint64_t now_unix_ns);
 int emurx_ingest_ping(emurx_t* h, uint32_t slot, emurx_ping_out* out);
+/* The flow decisions on a slot.  emurx_ingest_set_flows(h, slot, on) holds for the slot's later
+   submits; on: 0 = off (the default), anything else on.  The stage is independent of
+   emurx_ingest_set_answers: either may be on without the other.  With flows on, the slot's k_rx
+   writes the per-frame flow words (emurx_dev_out.flow); the batch always takes the copy + launches
+   pipeline (res.one_launch is 0, as with answers); emurx_ingest_submit returns EMURX_ENOSPC for
+   messages that end past cfg.max_bytes.  Behind the queue pack, and behind the answer stages and
+   the ping stage where the slot has them on, emurx_ftstat_dev runs over the slot's frames,
+   descriptors, records and flow words with an ev_cap no batch can exceed: a folded frame is at
+   least 42 bytes long (l3 >= 14, an IPv4 header and 8 bytes of UDP, or more), so a batch has at
+   most min(emurx_ftstat_max_events(h), max_bytes / 42 + 1) events.  The fold's scratch is the
+   handle's: with or without answers the stage takes part in the hand-off of the handle's scratches
+   from slot to slot (it waits for the previous slot's event and records its own behind the fold),
+   and a caller's own emurx_ftstat_dev must not overlap a slot's batch that has flows on.  Then one
+   launch reads the stage's counts on the device and writes the info words, the flow and outcome
+   arrays and the events produced, and no more, into pinned memory the slot owns.  The first call
+   with on != 0 allocates everything for cfg.max_frames and cfg.max_bytes: no submit allocates or
+   synchronises for it.  A slot with a batch in flight or slot >= EMURX_INGEST_SLOTS are
+   EMURX_EINVAL; a host-only handle EMURX_EDEVICE.  emurx_ingest_flows(h, slot, &out), after the
+   emurx_ingest_wait of that batch, points `out` at library-owned memory, valid until the slot's
+   next submit; flow, outcome and the events' first / last are in res.rec's numbering, also when
+   messages fell short of the frames they announced.  It returns EMURX_ENOENT when the slot's last
+   batch ran without flows, EMURX_EINVAL before any wait or with a batch in flight.
+   emurx_ingest_result, emurx_answers and emurx_ping_out are the same with flows on or off (but
+   res.one_launch). */
+typedef struct emurx_flows_out {
+    const uint32_t* flow;         /* [n_frames] EMURX_FLOW_* / flow id */
+    const uint8_t* outcome;       /* [n_frames] enum emurx_ft | EMURX_FT_V6 */
+    const emurx_ft_ev* ev;        /* [n_ev] ascending `last` */
+    uint32_t n_ev;
+    uint64_t info[EMURX_FT_INFO_WORDS];
+} emurx_flows_out;
+int emurx_ingest_set_flows(emurx_t* h, uint32_t slot, uint32_t on);
+int emurx_ingest_flows(emurx_t* h, uint32_t slot, emurx_flows_out* out);
 
 /* ParserStats delta from an outcome histogram (pure host arithmetic). */
 void emurx_hist_to_counters(const uint64_t hist[2 * EMURX_HIST_BINS], emurx_counters* out);

@@ -62,6 +62,10 @@ GROUPS = [
                           "emurx_ingest_ping"],
      "`HandleEchoReply` / `HandleDestinationUnreachable` `icmp/icmp.go:328-393`, `ipv6/ipv6.go:359-462`, "
      "`Ping.HandleEchoReply` `ping/ping.go:246-304`"),
+    ("Device fold of refused transport frames", ["emurx_ftstat_dev", "emurx_ftstat_max_events", "emurx_ingest_set_flows",
+                                                 "emurx_ingest_flows"],
+     "`HandleRxTransPacket` `transport/plugin_transport.go:74-128`, `TransportCtx.handleRxPacket` "
+     "`transport/client_ctx.go:912-969`, `handleRxTcpNewFlow` / `handleRxUdpNewFlow` `:829-906`, `ftStats` `:158-197`"),
     ("Measurement", ["emurx_set_timing", "emurx_kernel_times", "emurx_copy_ceiling_dev", "emurx_last_stage",
                      "emurx_last_uniform", "emurx_last_trim", "emurx_last_txz"],
      "(bench.py; `emurx_copy_ceiling_dev` is the measured HBM copy ceiling beside the roofline)"),

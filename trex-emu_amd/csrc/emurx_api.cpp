@@ -147,8 +147,21 @@ struct IngestSlot {
     View<uint64_t> h_pinfo;
     View<uint8_t> h_pngo;
     View<emurx_ping_ev> h_pev;
+    // the flow stage (emurx_ingest_set_flows): k_rx's flow words and the fold's outputs, sized once
+    bool flw_on = false, flw_batch = false;  // the setting for later submits; the batch in flight / last waited for
+    uint32_t flw_ev_cap = 0;                 // events the device array and the pinned block hold
+    DevBuf<uint32_t> d_flow;
+    DevBuf<emurx_ft_ev> d_fev;
+    DevBuf<uint64_t> d_finfo;
+    DevBuf<uint8_t> d_fto;
+    PinBuf<uint8_t> h_flw;                   // the pinned block (k_ft_out writes it)
+    View<uint64_t> h_finfo;
+    View<uint32_t> h_flow;
+    View<uint8_t> h_fto;
+    View<emurx_ft_ev> h_fev;
     void release() {
         if (st) (void)hipStreamSynchronize(st);
+        d_flow.release(); d_fev.release(); d_finfo.release(); d_fto.release(); h_flw.release();
         d_pev.release(); d_pinfo.release(); d_pngo.release(); h_png.release();
         d_rsp_out.release(); d_tx.release(); d_rsp_desc.release(); d_rsp_src.release(); d_tx_off.release();
         d_ainfo.release(); d_lev.release(); d_nsev.release(); h_ans.release();
@@ -239,7 +252,11 @@ struct emurx_ctx {
     // rows and its set are zero between calls, cleared like the learning set
     DevBuf<uint8_t> d_png;
     bool png_dirty = false;
-    // the answer stages of ingest slots (emurx_ingest_set_answers) share the four scratches above:
+    // the scratch of the fold of refused TCP / UDP frames (emurx_ftstat_dev), sized at emurx_open from
+    // max_frames: its accumulator rows and its set are zero between calls, cleared like the learning set
+    DevBuf<uint8_t> d_fts;
+    bool fts_dirty = false;
+    // the answer and flow stages of ingest slots (emurx_ingest_set_answers, _set_flows) share the scratches above:
     // each stage waits for the previous one's event and records its own
     hipEvent_t ans_ev = nullptr;
     bool ans_recorded = false;
@@ -664,7 +681,7 @@ int set_results(IngestSlot& s, uint32_t n, uint32_t nmsg, bool answers) {
     return EMURX_OK;
 }
 
-int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n);  // below, with the stages it enqueues
+int stage_chain(emurx_t* h, IngestSlot& s, uint32_t n);  // below: the answer stages and the flow stage of a slot
 
 int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nmsg) {
     IngestSlot& s = h->ing[slot];
@@ -696,7 +713,8 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     }
     base[nmsg] = (uint32_t)S;
     const uint32_t kinds = s.ans_kinds;
-    if (kinds && end > h->cfg.max_bytes) return EMURX_ENOSPC;  // the answer buffers are sized for max_bytes
+    const bool flows = s.flw_on;
+    if ((kinds || flows) && end > h->cfg.max_bytes) return EMURX_ENOSPC;  // the stages' buffers are sized for max_bytes
     const uint32_t n = (uint32_t)S, nt = ntiles(n);
     const size_t qcap = std::max<size_t>(queue_cap(n), EMURX_QUEUE_TILE);
     const size_t hw = (size_t)EMURX_HIST_SHARDS * 2 * EMURX_HIST_BINS;
@@ -711,8 +729,8 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     // the pipeline's histogram shards start zeroed (k_qscan leaves them zero)
     if (fresh_hist && !EMURX_HIP_OK(hipMemsetAsync(s.d_hist.p, 0, hw * sizeof(uint64_t), st))) return EMURX_EDEVICE;
     uint32_t trange[EMURX_SMALL_TILES];
-    // (a batch with answers takes the pipeline: the one-launch path leaves no frame in device memory)
-    if (h->ingest_small && !kinds && small_fits(ctl, nmsg, n, h->small_tiles, trange)) {
+    // (a batch with answers or flows takes the pipeline: the one-launch path leaves no frame in device memory)
+    if (h->ingest_small && !kinds && !flows && small_fits(ctl, nmsg, n, h->small_tiles, trange)) {
         // one launch: control words and messages read from the pinned buffers, every result
         // written into the pinned result buffers (no copies)
         if (!s.d_ticket.p) {
@@ -736,6 +754,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
         s.small = true;
         s.ans_batch = 0;
         s.png_batch = 0;
+        s.flw_batch = false;
         s.pending = true;
         s.nmsg = nmsg;
         s.slots = n;
@@ -747,7 +766,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     if (!ok) return EMURX_EDEVICE;
     if (emurx_launch_zmq_walk(s.d_buf.p, s.d_ctl.p, nmsg, s.d_desc.p, s.d_stat.p, st)) return EMURX_EDEVICE;
     if (n) {
-        const emurx_dev_out o{s.d_rec.p, s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, s.d_hist.p};
+        const emurx_dev_out o{s.d_rec.p, s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, s.d_hist.p, flows ? s.d_flow.p : nullptr};
         const uint32_t stage = choose_stage(h);
         if (emurx_launch_batch(s.d_buf.p, s.d_desc.p, n, h->tables(), true, o, st, nullptr, stage,
                                h->d_stage_fb.p, h->stage_gen, h->uniform) ||
@@ -757,7 +776,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     if (emurx_launch_queue_pack(s.d_qlist.p, (uint32_t)qcap, s.d_tile_cnt.p, n, s.d_seg_off.p, s.d_packed.p,
                                 s.d_qoff.p, s.d_hist.p, s.d_hist_out.p, st))
         return EMURX_EDEVICE;
-    if (kinds && (rc = answer_chain(h, s, n))) return rc;
+    if ((kinds || flows) && (rc = stage_chain(h, s, n))) return rc;
     // every result in one copy: records, descriptors, packed queues, status, qoff, histogram
     ok = EMURX_HIP_OK(hipMemcpyAsync(s.h_res.p, s.d_res.p, s.res_bytes, D2H, st)) &&
          EMURX_HIP_OK(hipEventRecord(s.done, st));
@@ -765,6 +784,7 @@ int ingest_submit(emurx_t* h, uint32_t slot, const emurx_msg* msgs, uint32_t nms
     s.small = false;
     s.ans_batch = kinds;
     s.png_batch = kinds ? s.png_fams : 0;
+    s.flw_batch = flows;
     s.pending = true;
     s.nmsg = nmsg;
     s.slots = n;
@@ -797,7 +817,9 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
     s.pending = false;
     s.waited = true;
     const uint32_t ans = s.ans_batch, png = s.png_batch;
+    const bool flw = s.flw_batch;
     s.ans_batch = s.png_batch = 0;  // set again below, once the answers are checked and renumbered
+    s.flw_batch = false;
     if (!(s.small && h->ingest_spin && spin_done(s.h_done.p, s.seq)) && !EMURX_HIP_OK(hipEventSynchronize(s.done)))
         return EMURX_EDEVICE;
     memset(res, 0, sizeof(*res));
@@ -825,6 +847,10 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
                 for (View<uint8_t>* v : {&s.h_rspo, &s.h_lrno, &s.h_donef})
                     if (ans) memmove(v->p + c, v->p + base[m], f);
                 if (png) memmove(s.h_pngo.p + c, s.h_pngo.p + base[m], f);
+                if (flw) {
+                    memmove(s.h_fto.p + c, s.h_fto.p + base[m], f);
+                    memmove(s.h_flow.p + c, s.h_flow.p + base[m], (size_t)f * sizeof(uint32_t));
+                }
             }
             for (uint32_t k = 0; k < f; ++k) s.remap[base[m] + k] = c + k;
             c += f;
@@ -863,6 +889,17 @@ int ingest_wait(emurx_t* h, uint32_t slot, emurx_ingest_result* res) {
             s.png_batch = png;
         }
         s.ans_batch = ans;
+    }
+    if (flw) {
+        const uint64_t nev = s.h_finfo.p[0];
+        if (nev > s.flw_ev_cap) return EMURX_EDEVICE;
+        for (uint64_t k = 0; k < nev && nf < s.slots; ++k) {  // slot numbers -> the closed numbering (monotone)
+            for (uint32_t* j : {&s.h_fev.p[k].first, &s.h_fev.p[k].last}) {
+                if (*j >= s.slots || s.remap[*j] == EMURX_ID_NONE) return EMURX_EDEVICE;
+                *j = s.remap[*j];
+            }
+        }
+        s.flw_batch = true;
     }
     memcpy(res->qoff, s.h_qoff.p, sizeof(res->qoff));
     if (res->qoff[EMURX_NUM_QUEUES] != nf) return EMURX_EDEVICE;
@@ -971,6 +1008,11 @@ int emurx_open(const emurx_cfg* cfg, emurx_t** out) {
         emurx_close(h);
         return EMURX_ENOMEM;
     }
+    if (h->d_fts.alloc(emurx_ft_scratch_bytes(cfg->max_frames)) ||
+        emurx_ft_scratch_clear(h->d_fts.p, cfg->max_frames, h->stream) || !EMURX_HIP_OK(hipStreamSynchronize(h->stream))) {
+        emurx_close(h);
+        return EMURX_ENOMEM;
+    }
     emurx_t::RouteScratch* rs = nullptr;
     if ((rc = ship_tables(h, h->stream)) || (rc = route_scratch(h, cfg->max_frames, h->stream, &rs)) == EMURX_ENOMEM) {
         emurx_close(h);
@@ -1008,6 +1050,7 @@ void emurx_close(emurx_t* h) {
     h->d_lrn.release();
     h->d_nss.release();
     h->d_png.release();
+    h->d_fts.release();
     h->txz_fb.release();
     if (h->txz_ev) (void)hipEventDestroy(h->txz_ev);
     if (h->ans_ev) (void)hipEventDestroy(h->ans_ev);
@@ -1724,6 +1767,34 @@ int emurx_ping_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc
     return EMURX_OK;
 }
 
+uint32_t emurx_ftstat_max_events(const emurx_t* h) { return h ? std::min(h->cfg.max_frames, h->cfg.max_clients) : 0; }
+
+int emurx_ftstat_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, const emurx_rec* d_rec,
+                     const uint32_t* d_flow, uint32_t n, emurx_ft_ev* d_ev, uint32_t ev_cap, uint8_t* d_outcome,
+                     uint64_t* d_info, void* stream) {
+    if (!h || !d_info || !d_ev || (n && (!d_frames || !d_desc || !d_rec || !d_flow))) return EMURX_EINVAL;
+    if (ev_cap == 0 || ev_cap > emurx_ftstat_max_events(h)) return EMURX_EINVAL;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES || ((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ev & 7) ||
+        ((uintptr_t)d_info & 7) || ((uintptr_t)d_flow & 3))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;  // the scratch is sized at emurx_open
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // no table is read, but the records and flow words are a classify's: behind the shipment like the call they come from
+    if ((rc = not_capturing(st)) || (rc = prepare_read(h, st))) return rc;
+    if (h->fts_dirty) {
+        if (emurx_ft_scratch_clear(h->d_fts.p, h->cfg.max_frames, st)) return EMURX_EDEVICE;
+        h->fts_dirty = false;
+    }
+    if (emurx_launch_ftstat(d_frames, d_desc, d_rec, d_flow, n, h->cfg.max_ns, h->cfg.max_clients, d_ev, ev_cap, d_outcome,
+                            d_info, h->d_fts.p, h->cfg.max_frames, st)) {
+        h->fts_dirty = true;
+        return EMURX_EDEVICE;
+    }
+    return EMURX_OK;
+}
+
 uint32_t emurx_ns_owner(const uint8_t key[12], uint32_t n_parts) {
     if (!key || n_parts == 0) return 0;
     return emurx_owner(emurx_tk_hash(le32(key), le32(key + 4), le32(key + 8)), n_parts);
@@ -1785,56 +1856,61 @@ AnsCaps answer_caps(const emurx_t* h) {
     return c;
 }
 
-// The answer chain of a batch of n descriptor slots, on the slot's stream behind k_rx and the
-// queue pack: respond, the counted framing of the replies, learn, nsstat (serialised across
-// slots: the four stages' scratch is the handle's), then k_ans_out.  No allocation and no host
-// synchronisation: emurx_ingest_set_answers sized everything.
-int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
+// The four info blocks of a slot's answer stages, laid out in d_ainfo as the answer block's head
+struct AnsInfo {
+    uint64_t *rsp, *lrn, *nss, *tx;
+};
+AnsInfo answer_info(IngestSlot& s) {
+    uint64_t* p = s.d_ainfo.p;
+    return {p, p + EMURX_ANS_HEAD_LRN, p + EMURX_ANS_HEAD_NSS, p + EMURX_ANS_HEAD_TX};
+}
+
+// The answer stages of a batch of n descriptor slots (answers on): respond, the counted framing of
+// the replies, learn, nsstat and, where the slot has it on, the ping fold.
+int answer_stages(emurx_t* h, IngestSlot& s, uint32_t n) {
     hipStream_t st = s.st;
     const uint32_t kinds = s.ans_kinds;
-    uint64_t* rsp_info = s.d_ainfo.p;
-    uint64_t* lrn_info = rsp_info + EMURX_ANS_HEAD_LRN;
-    uint64_t* nss_info = rsp_info + EMURX_ANS_HEAD_NSS;
-    uint64_t* tx_info = rsp_info + EMURX_ANS_HEAD_TX;
-    if (n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
-    if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
+    const AnsInfo inf = answer_info(s);
     // the slot's time of day rides the launch as an argument: batches in flight keep their own
     int rc = respond_kinds(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, EMURX_RSPK_ALL_TS, s.ans_time,
                            EMURX_RSP_INFO_WORDS, s.d_rsp_out.p, s.ans_rsp_cap, s.d_rsp_desc.p, s.d_rsp_src.p, s.d_rspo.p,
-                           rsp_info, st);
+                           inf.rsp, st);
     if (rc) return rc;
-    if ((rc = emurx_tx_zmq_counted_dev(h, s.d_rsp_out.p, s.d_rsp_desc.p, n, rsp_info, s.d_tx.p, s.ans_tx_cap,
-                                       s.d_tx_off.p, tx_info, st)))
+    if ((rc = emurx_tx_zmq_counted_dev(h, s.d_rsp_out.p, s.d_rsp_desc.p, n, inf.rsp, s.d_tx.p, s.ans_tx_cap,
+                                       s.d_tx_off.p, inf.tx, st)))
         return rc;
     const uint32_t lk = ((kinds & EMURX_RSPK_ARP) ? EMURX_LRNK_ARP : 0u) | ((kinds & EMURX_RSPK_ND) ? EMURX_LRNK_ND : 0u);
     if (lk) {
         rc = emurx_learn_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, lk, s.d_lev.p, emurx_learn_max_events(h),
-                             s.d_lrno.p, lrn_info, st);
+                             s.d_lrno.p, inf.lrn, st);
     } else {  // nothing to learn from: every outcome EMURX_LRN_NONE, no event
-        rc = EMURX_HIP_OK(hipMemsetAsync(lrn_info, 0, EMURX_LRN_INFO_WORDS * sizeof(uint64_t), st)) &&
+        rc = EMURX_HIP_OK(hipMemsetAsync(inf.lrn, 0, EMURX_LRN_INFO_WORDS * sizeof(uint64_t), st)) &&
                      (!n || EMURX_HIP_OK(hipMemsetAsync(s.d_lrno.p, 0, n, st)))
                  ? EMURX_OK
                  : EMURX_EDEVICE;
     }
     if (rc) return rc;
     if ((rc = emurx_nsstat_ts_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, kinds, s.d_rspo.p, s.d_lrno.p, s.d_nsev.p,
-                                  emurx_nsstat_max_events(h), s.d_donef.p, nss_info, st)))
+                                  emurx_nsstat_max_events(h), s.d_donef.p, inf.nss, st)))
         return rc;
     // the ping stage, with the slot's own time of day as a launch argument
-    const uint32_t fams = s.png_fams;
-    if (fams && (rc = emurx_ping_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, fams, s.png_now, s.d_pev.p, emurx_ping_max_events(h),
-                                     s.d_pngo.p, s.d_pinfo.p, st)))
-        return rc;
-    // the shared scratch is free again: the next slot's stage may start while this one copies out
-    if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
-    h->ans_recorded = true;
-    if (fams && emurx_launch_ping_out(s.d_pinfo.p, s.d_pev.p, s.d_pngo.p, n, s.png_ev_cap, reinterpret_cast<uint8_t*>(s.h_pinfo.p),
-                                      reinterpret_cast<uint8_t*>(s.h_pev.p), s.h_pngo.p, st))
+    if (s.png_fams)
+        rc = emurx_ping_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, n, s.png_fams, s.png_now, s.d_pev.p, emurx_ping_max_events(h),
+                            s.d_pngo.p, s.d_pinfo.p, st);
+    return rc;
+}
+
+// What the answer stages produced, into the slot's pinned blocks: k_png_out, then k_ans_out.
+int answer_out(IngestSlot& s, uint32_t n) {
+    hipStream_t st = s.st;
+    const AnsInfo inf = answer_info(s);
+    if (s.png_fams && emurx_launch_ping_out(s.d_pinfo.p, s.d_pev.p, s.d_pngo.p, n, s.png_ev_cap, reinterpret_cast<uint8_t*>(s.h_pinfo.p),
+                                            reinterpret_cast<uint8_t*>(s.h_pev.p), s.h_pngo.p, st))
         return EMURX_EDEVICE;
-    const emurx_ans_out a{reinterpret_cast<const unsigned long long*>(rsp_info),
-                          reinterpret_cast<const unsigned long long*>(tx_info),
-                          reinterpret_cast<const unsigned long long*>(lrn_info),
-                          reinterpret_cast<const unsigned long long*>(nss_info),
+    const emurx_ans_out a{reinterpret_cast<const unsigned long long*>(inf.rsp),
+                          reinterpret_cast<const unsigned long long*>(inf.tx),
+                          reinterpret_cast<const unsigned long long*>(inf.lrn),
+                          reinterpret_cast<const unsigned long long*>(inf.nss),
                           s.d_tx.p,
                           reinterpret_cast<const unsigned long long*>(s.d_tx_off.p),
                           s.d_rsp_src.p,
@@ -1851,6 +1927,33 @@ int answer_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
                           s.ans_ev_cap,
                           s.ans_ns_cap};
     return emurx_launch_ans_out(a, n, st) ? EMURX_EDEVICE : EMURX_OK;
+}
+
+// The stage chain of a batch of n descriptor slots, on the slot's stream behind k_rx and the queue
+// pack, for a slot with answers on, flows on or both: the answer stages, then the fold of the
+// refused transport frames (emurx_ingest_set_flows), serialised across slots because the stages'
+// scratch is the handle's (each chain waits for the previous one's event and records its own
+// behind its last fold), then the launches that copy out.  No allocation and no host
+// synchronisation: emurx_ingest_set_answers / _set_ping / _set_flows sized everything.
+int stage_chain(emurx_t* h, IngestSlot& s, uint32_t n) {
+    hipStream_t st = s.st;
+    const bool answers = s.ans_kinds != 0, flows = s.flw_on;
+    if (n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
+    if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
+    int rc;
+    if (answers && (rc = answer_stages(h, s, n))) return rc;
+    if (flows && (rc = emurx_ftstat_dev(h, s.d_buf.p, s.d_desc.p, s.d_rec.p, s.d_flow.p, n, s.d_fev.p, s.flw_ev_cap, s.d_fto.p,
+                                        s.d_finfo.p, st)))
+        return rc;
+    // the shared scratch is free again: the next slot's stages may start while this one copies out
+    if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
+    h->ans_recorded = true;
+    if (answers && (rc = answer_out(s, n))) return rc;
+    if (flows && emurx_launch_ft_out(s.d_finfo.p, s.d_fev.p, s.d_flow.p, s.d_fto.p, n, s.flw_ev_cap,
+                                     reinterpret_cast<uint8_t*>(s.h_finfo.p), reinterpret_cast<uint8_t*>(s.h_fev.p),
+                                     reinterpret_cast<uint8_t*>(s.h_flow.p), s.h_fto.p, st))
+        return EMURX_EDEVICE;
+    return EMURX_OK;
 }
 
 // emurx_ingest_set_answers and emurx_ingest_set_answers_ts: `kinds` out of the entry point's `allowed`
@@ -1970,6 +2073,58 @@ int emurx_ingest_ping(emurx_t* h, uint32_t slot, emurx_ping_out* out) {
     out->n_ev = (uint32_t)s.h_pinfo.p[0];
     out->outcome = s.h_pngo.p;
     memcpy(out->info, s.h_pinfo.p, sizeof(out->info));
+    return EMURX_OK;
+}
+
+int emurx_ingest_set_flows(emurx_t* h, uint32_t slot, uint32_t on) {
+    if (!h || slot >= EMURX_INGEST_SLOTS) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    IngestSlot& s = h->ing[slot];
+    if (s.pending) return EMURX_EINVAL;
+    if (!on || s.h_flw.p) {  // off, or sized by an earlier call
+        s.flw_on = on != 0;
+        return EMURX_OK;
+    }
+    // everything the stage needs, now: no submit allocates or synchronises for it.  A folded frame
+    // is at least 42 bytes long (l3 >= 14, 20 bytes of IPv4 header and 8 of UDP, or more), so a
+    // batch has at most max_bytes / 42 events beside emurx_ftstat_max_events: the fold's ev_cap,
+    // which no batch can exceed, and the capacity of the pinned block.
+    if (!h->ans_ev && !EMURX_HIP_OK(hipEventCreateWithFlags(&h->ans_ev, hipEventDisableTiming))) return EMURX_EDEVICE;
+    const uint32_t mf = std::min<uint32_t>(h->cfg.max_frames, EMURX_TX_ZMQ_MAX_FRAMES - 1);
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(emurx_ftstat_max_events(h), (uint64_t)h->cfg.max_bytes / 42 + 1);
+    // the device arrays are readable to the next 16-byte boundary past any count (k_ft_out)
+    if (s.d_flow.alloc((size_t)mf + 4) || s.d_fev.alloc((size_t)cap + 1) || s.d_finfo.alloc(EMURX_FT_INFO_WORDS) ||
+        s.d_fto.alloc((size_t)mf + 16))
+        return EMURX_ENOMEM;
+    if (!EMURX_HIP_OK(hipMemset(s.d_finfo.p, 0, EMURX_FT_INFO_WORDS * sizeof(uint64_t)))) return EMURX_EDEVICE;
+    auto carve = [&](uint8_t* block) {
+        emurx_carver k(block);
+        s.h_finfo.p = k.take<uint64_t>(EMURX_FT_INFO_WORDS);
+        s.h_flow.p = k.take<uint32_t>((size_t)mf + 4);
+        s.h_fto.p = k.take<uint8_t>((size_t)mf + 16);
+        s.h_fev.p = k.take<emurx_ft_ev>(cap);
+        return k.bytes();
+    };
+    if (s.h_flw.alloc(carve(nullptr))) return EMURX_ENOMEM;
+    carve(s.h_flw.p);
+    memset(s.h_finfo.p, 0, EMURX_FT_INFO_WORDS * sizeof(uint64_t));
+    s.flw_ev_cap = cap;
+    s.flw_on = true;
+    return EMURX_OK;
+}
+
+int emurx_ingest_flows(emurx_t* h, uint32_t slot, emurx_flows_out* out) {
+    if (!h || !out || slot >= EMURX_INGEST_SLOTS) return EMURX_EINVAL;
+    const IngestSlot& s = h->ing[slot];
+    if (s.pending || !s.waited) return EMURX_EINVAL;
+    if (!s.flw_batch) return EMURX_ENOENT;
+    memset(out, 0, sizeof(*out));
+    out->flow = s.h_flow.p;
+    out->outcome = s.h_fto.p;
+    out->ev = s.h_fev.p;
+    out->n_ev = (uint32_t)s.h_finfo.p[0];
+    memcpy(out->info, s.h_finfo.p, sizeof(out->info));
     return EMURX_OK;
 }
 

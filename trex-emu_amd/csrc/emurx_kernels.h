@@ -239,6 +239,19 @@ int emurx_launch_ping(const uint8_t* frames, const emurx_desc* desc, const emurx
                       uint64_t now_unix_ns, const emurx_dev_tables& T, emurx_ping_ev* ev, uint32_t ev_cap, uint8_t* outcome,
                       uint64_t* info, void* scratch, uint32_t max_frames, hipStream_t st);
 
+// The fold of refused TCP / UDP frames (emurx_ftstat.hip): see emurx_ftstat_dev.  scratch:
+// emurx_ft_scratch_bytes(max_frames) bytes, whose accumulator rows and owner words
+// emurx_ft_scratch_clear zeroes before the first call; every call leaves them zero.  n <=
+// max_frames.  Four launches.
+size_t emurx_ft_scratch_bytes(uint32_t max_frames);
+int emurx_ft_scratch_clear(void* scratch, uint32_t max_frames, hipStream_t st);
+int emurx_launch_ftstat(const uint8_t* frames, const emurx_desc* desc, const emurx_rec* rec, const uint32_t* flow, uint32_t n,
+                        uint32_t max_ns, uint32_t max_clients, emurx_ft_ev* ev, uint32_t ev_cap, uint8_t* outcome,
+                        uint64_t* info, void* scratch, uint32_t max_frames, hipStream_t st);
+// a slot's flow stage to its pinned block (k_ft_out): info, n flow words, n outcome bytes, min(info[0], ev_cap) events
+int emurx_launch_ft_out(const uint64_t* info, const emurx_ft_ev* ev, const uint32_t* flow, const uint8_t* outcome, uint32_t n,
+                        uint32_t ev_cap, uint8_t* h_info, uint8_t* h_ev, uint8_t* h_flow, uint8_t* h_outcome, hipStream_t st);
+
 // Tx ZMQ framing (emurx_txzmq.hip): see emurx_tx_zmq_dev.  scratch: emurx_txz_scratch_bytes(n).
 size_t emurx_txz_scratch_bytes(uint32_t n);
 // variant: the write kernel's image (EMURX_TXZ_*, emurx_tx_zmq_dev's feedback choice); feedback:

@@ -170,6 +170,18 @@ FLOW_NONE, FLOW_NO_CTX, FLOW_NO_SYN, FLOW_NO_SERVER, FLOW_NEW = (0xFFFFFFFF, 0xF
                                                                 0xFFFFFFF2, 0xFFFFFFF3)
 FLOW_UNKNOWN = 0xFFFFFFF4  # emurx_lookup_dev: the head came without its c5tuplekey
 FLOW_ID_MAX = 0xFFFFFFEF
+# enum emurx_ft: the per-frame outcome of emurx_ftstat_dev (& 7), FT_V6 beside outcomes 1..3
+FT_NONE, FT_NO_SYN, FT_NO_SRV_TCP, FT_NO_SRV_UDP, FT_ERR = range(5)
+FT_V6 = 0x08
+# enum emurx_ftc: the ftStats words of emurx_ft_ev.cnt (client_ctx.go:158-197)
+FTC_LOOKUP_V4, FTC_LOOKUP_V6, FTC_NEW_TCP, FTC_NEW_TCP_NO_SYN, FTC_NEW_UDP, FTC_NEW_NO_CB = range(6)
+FTC_WORDS = 7
+FTC_GO = ["ft_lookupv4", "ft_lookupv6", "ft_new_tcp", "ft_new_tcp_no_syn", "ft_new_udp", "ft_new_no_cb"]
+FT_INFO_WORDS = 8
+# emurx_ft_ev: one event per client with a refused TCP / UDP frame
+FT_EV_DTYPE = np.dtype([("ns_id", "<u4"), ("client_id", "<u4"), ("first", "<u4"), ("last", "<u4"), ("frames", "<u4"),
+                        ("cnt", "<u4", FTC_WORDS)])
+assert FT_EV_DTYPE.itemsize == 48
 # emurx_client_spec (ctx_client_add list entry)
 CLIENT_SPEC_DTYPE = np.dtype([("ns_id", "<u4"), ("client_id", "<u4"), ("plugin_mask", "<u4"), ("mac", "u1", 6),
                               ("ipv4", "u1", 4), ("ipv6", "u1", 16), ("dhcpv6", "u1", 16), ("pad", "u1", 2)])
@@ -215,6 +227,12 @@ class Answers(C.Structure):
 class PingOut(C.Structure):
     """emurx_ping_out: a slot's ping fold (emurx_ingest_ping); pointers into library memory."""
     _fields_ = [("ev", C.c_void_p), ("n_ev", C.c_uint32), ("outcome", C.c_void_p), ("info", C.c_uint64 * PNG_INFO_WORDS)]
+
+
+class FlowsOut(C.Structure):
+    """emurx_flows_out: a slot's flow decisions (emurx_ingest_flows); pointers into library memory."""
+    _fields_ = [("flow", C.c_void_p), ("outcome", C.c_void_p), ("ev", C.c_void_p), ("n_ev", C.c_uint32),
+                ("info", C.c_uint64 * FT_INFO_WORDS)]
 
 
 class DevOut(C.Structure):
@@ -313,6 +331,10 @@ SIGNATURES = [
     ("emurx_ingest_set_ping", C.c_int, [_P, C.c_uint32, C.c_uint32]),
     ("emurx_ingest_set_now", C.c_int, [_P, C.c_uint32, C.c_uint64]),
     ("emurx_ingest_ping", C.c_int, [_P, C.c_uint32, C.POINTER(PingOut)]),
+    ("emurx_ftstat_max_events", C.c_uint32, [_P]),
+    ("emurx_ftstat_dev", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_ingest_set_flows", C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    ("emurx_ingest_flows", C.c_int, [_P, C.c_uint32, C.POINTER(FlowsOut)]),
     ("emurx_flow_add", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32, C.c_uint32]),
     ("emurx_flow_remove", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint32]),
     ("emurx_server_add", C.c_int, [_P, C.c_uint32, C.c_uint16, C.c_uint8]),
@@ -334,7 +356,8 @@ SIGNATURES = [
 # bench.py against two builds) may lack; calling one it lacks is an AttributeError
 OPTIONAL = {"emurx_last_uniform", "emurx_last_trim", "emurx_respond_ts_dev", "emurx_nsstat_ts_dev",
             "emurx_ingest_set_answers_ts", "emurx_ingest_set_time", "emurx_ping_max_events", "emurx_ping_dev",
-            "emurx_ingest_set_ping", "emurx_ingest_set_now", "emurx_ingest_ping"}
+            "emurx_ingest_set_ping", "emurx_ingest_set_now", "emurx_ingest_ping", "emurx_ftstat_max_events",
+            "emurx_ftstat_dev", "emurx_ingest_set_flows", "emurx_ingest_flows"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
 TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 
@@ -373,7 +396,7 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
-           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_ftstat.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()

@@ -316,6 +316,26 @@ class RxPath:
         return dict(ev=copy(a.ev, a.n_ev, abi.PING_EV_DTYPE), outcome=copy(a.outcome, n_frames, np.uint8),
                     info=np.array(a.info, np.uint64))
 
+    def ingest_set_flows(self, slot: int, on: bool) -> None:
+        """Return the per-frame flow words and fold the refused TCP / UDP frames on the slot's later
+        batches; independent of answers (include/emu_rx.h emurx_ingest_set_flows)."""
+        abi.check(self.lib.emurx_ingest_set_flows(self.h, slot, 1 if on else 0), "ingest_set_flows")
+
+    def ingest_flows(self, slot: int, n_frames: int) -> dict:
+        """The flow decisions of the slot's batch, after its ingest_wait (n_frames: that result's
+        n), as numpy copies: flow u32 [n_frames], outcome u8 [n_frames], ev (abi.FT_EV_DTYPE,
+        ascending `last`), info."""
+        a = abi.FlowsOut()
+        abi.check(self.lib.emurx_ingest_flows(self.h, slot, C.byref(a)), "ingest_flows")
+
+        def copy(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            b = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dt).itemsize,))
+            return b.view(dt).copy()
+        return dict(flow=copy(a.flow, n_frames, np.uint32), outcome=copy(a.outcome, n_frames, np.uint8),
+                    ev=copy(a.ev, a.n_ev, abi.FT_EV_DTYPE), info=np.array(a.info, np.uint64))
+
     # ---- tx-side checksum generation ------------------------------------------------------
     def tx_checksum_dev(self, frames, desc, n: int, status=None, stream=None):
         """Rewrite the checksums selected by each TX_DESC_DTYPE descriptor, in place on the
@@ -414,6 +434,20 @@ class RxPath:
         return abi.check(self.lib.emurx_ping_dev(self.h, _addr(frames), _addr(desc), _addr(rec), n, fams, now_unix_ns,
                                                  _addr(ev), ev_cap, _addr(outcome), _addr(info), _stream(stream)),
                          "ping_dev")
+
+    def ftstat_max_events(self) -> int:
+        """The largest ev_cap ftstat_dev takes: min(max_frames, max_clients)."""
+        return int(self.lib.emurx_ftstat_max_events(self.h))
+
+    def ftstat_dev(self, frames, desc, rec, flow, n: int, ev, ev_cap: int, outcome, info, stream=None):
+        """The TCP / UDP frames of a classified batch that the transport plugin refuses, folded on the
+        device into one event per client (include/emu_rx.h emurx_ftstat_dev): flow u32 [n] is the
+        flow array of the classify_dev call that wrote rec; ev abi.FT_EV_DTYPE [ev_cap], written in
+        ascending `last`; outcome u8 [n] (abi.FT_* | abi.FT_V6, or None); info u64[abi.FT_INFO_WORDS]
+        {events written, distinct clients, overflow, frames NO_SYN, NO_SRV_TCP, NO_SRV_UDP, ERR,
+        candidates left at NONE}.  On overflow (distinct clients > ev_cap) no event is written."""
+        return abi.check(self.lib.emurx_ftstat_dev(self.h, _addr(frames), _addr(desc), _addr(rec), _addr(flow), n, _addr(ev),
+                                                   ev_cap, _addr(outcome), _addr(info), _stream(stream)), "ftstat_dev")
 
     # ---- Namespace-partitioned exchange ---------------------------------------------------
     def classify_route_dev(self, frames, desc, n: int, rec, qlist, qcap: int, tile_cnt, hist, n_parts: int,
