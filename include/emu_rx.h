@@ -598,6 +598,98 @@ int emurx_tx_zmq_counted_dev(emurx_t* h, const uint8_t* d_frames, const emurx_de
                              uint32_t n_max, const uint64_t* d_count,
                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_msg_off, uint64_t* d_info, void* stream);
 
+/* ---- the tx planner: emurx_tx_desc from the frames themselves ------------------------------
+   emurx_tx_checksum_dev wants {l3, l4, osize, ops, nh} per frame; the plugins' send paths know
+   them while they build a frame, a caller that only holds finished frames does not.  The planner
+   derives them with the header walk of the rx parser (src/emu/core/parser.go), without its
+   checksum tests, so that what the library sends it also parses.  p: the frame, len: its length,
+   be16: a big-endian byte pair.  Outcome per frame (enum emurx_txp) and descriptor:
+     L2    len < 14 -> BAD.  EtherType at 12; each 0x8100 / 0x88a8 tag advances 4 bytes and needs
+           the next EtherType inside len (else BAD); a third tag -> BAD (parser.go:700-741 accepts
+           two).  l3 = the byte behind the EtherType.
+     IPv4  0x0800 (parser.go:771-862): BAD unless len >= l3 + 20, version 4, IHL * 4 >= 20,
+           len >= l3 + IHL * 4 and totlen >= IHL * 4.  From here on ops = EMURX_TX_IPV4_HDR and
+           l4 = l3 + IHL * 4 (the end of the header that op sums, the rx record's l4).
+           l3 + totlen != len -> LENGTH, the header op alone: the checksum call's L4 span is
+           p[l4:len], as the Go callers slice it (tcp_output.go:64-70, udp.go:143-150), so a frame
+           with bytes behind the datagram gets no L4 sum.
+           be16(p + l3 + 6) & 0x3fff (fragment offset or MF) or a protocol that is none of 6 / 17 /
+           1 -> HDR (IGMP with its 24-byte header, igmp.go:1179-1186, among them).
+           Else kind TCP4 / UDP4 / ICMP4, outcome L4; BAD when len < l4 + 20 / 8 / 4 (the bytes
+           up to the field the op clears).
+     IPv6  0x86dd (parser.go:864-952): BAD unless len >= l3 + 40 and version 6.
+           l3 + 40 + plen != len -> LENGTH with ops 0.
+           While the next header is one of {0, 43, 50, 51, 60, 135, 139, 140} (the parser's set):
+           the header is (p[o + 1] << 3) + 8 bytes; fewer than 8 bytes left or a header ending
+           past len -> BAD.  A final next header 6 / 17 / 58 -> TCP6 / UDP6 / ICMP6, outcome L4,
+           osize = l4 - l3 - 40 and, when osize > 0, ops |= EMURX_TX_V6_NH with nh = that next
+           header (ipv6/mld.go:1271); the same minimum lengths (ICMPv6: 4).  Any other next
+           header (44 and 59 among them) -> NONE.
+     else  ARP, EAPOL, PPPoE and the rest -> NONE, ops 0.
+   EMURX_TXP_UDP0_KEEP: a UDP checksum field that is 00 00 stays (IPv4: HDR, IPv6: NONE), for a
+   caller whose plugins still run their own checksum calls, where a zero field means "not used"
+   (DHCP sends it so); without the flag the field is computed.
+   d_txdesc[i] = {off, len, l3, l4, osize, ops, nh, pad 0}, off and len from d_desc[i]; every
+   field not named above is 0 (BAD, NONE and the IPv6 LENGTH: all of them), so the array compares
+   bytewise.  d_outcome [n] may be NULL; d_info (u64[EMURX_TXP_INFO_WORDS]) = frames per outcome
+   in enum order, then zeros; n == 0 writes a zero d_info.  d_desc 8-byte and d_txdesc 16-byte
+   aligned; frames are read as the aligned 16-byte blocks that hold their first 96 bytes, and
+   bytewise past that (IPv6 extension chains alone get there).  n > cfg.max_frames is
+   EMURX_ENOMEM; a NULL pointer, an unknown flag bit, a misaligned array or a capturing stream
+   EMURX_EINVAL; a host-only handle EMURX_EDEVICE.  One clear and one launch on `stream`, no host
+   synchronisation and no allocation. */
+#define EMURX_TXP_UDP0_KEEP 1u   /* flags: a UDP checksum field that is zero stays zero */
+enum emurx_txp { EMURX_TXP_NONE = 0, EMURX_TXP_HDR = 1, EMURX_TXP_L4 = 2,
+                 EMURX_TXP_LENGTH = 3, EMURX_TXP_BAD = 4 };
+#define EMURX_TXP_INFO_WORDS 8   /* frames per outcome in enum order, then zeros */
+int emurx_tx_plan_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n,
+                      uint32_t flags, emurx_tx_desc* d_txdesc, uint8_t* d_outcome /* may be NULL */,
+                      uint64_t* d_info, void* stream);
+
+/* ---- egress slots: tx for a caller without device memory -----------------------------------
+   What the ingest slots are to rx.  The caller appends outgoing frames and their descriptors
+   into the slot's pinned memory, submits, and gets back finished ZMQ messages: planned
+   (emurx_tx_plan_dev), checksummed (emurx_tx_checksum_dev) and framed as n Send calls and one
+   FlushTx would leave them (emurx_tx_zmq_dev).
+   emurx_egress_buffer returns the slot's pinned frame area (cfg.max_bytes bytes) and descriptor
+   array (cfg.max_frames entries).  The first call on a slot allocates everything the slot will
+   ever need (it waits for the device once and grows the handle's framing scratch to max_frames,
+   as emurx_ingest_set_answers does), so that no submit allocates or synchronises.
+   emurx_egress_submit: desc[i] = {off, len, vport, pad} names frame i in the frame area, the
+   frames in send order and not overlapping; `bytes` = the part of the frame area in use; flags:
+   the planner's.  It reads every descriptor once on the host, touches no frame byte, enqueues on
+   the slot's own stream
+     1. the H2D copies of `bytes` of frames and n descriptors,
+     2. the planner, 3. the checksum launch, in place on the device copy,
+     4. the framing (two launches) with out_cap = 8 n + bytes,
+     5. one launch (k_egr_out) that reads the framing's counts on the device and writes the
+        messages, msg_off, the two per-frame byte arrays and the info words straight into the
+        slot's pinned result block, no more than was produced,
+   and returns.  emurx_egress_wait blocks on the slot's event and points `res` at library memory,
+   valid until the slot's next submit.  No host synchronisation between submit and wait.
+   EMURX_EINVAL: a slot still in flight, slot >= EMURX_EGRESS_SLOTS, an unknown flag, a descriptor
+   that ends past `bytes`, a wait with nothing submitted; EMURX_ENOMEM: n > cfg.max_frames;
+   EMURX_ENOSPC: bytes > cfg.max_bytes; EMURX_EDEVICE: a host-only handle.
+   The framing scratch and the write image's choice belong to the handle, and ingest slots with
+   answers on use them too: an egress batch's framing joins the event hand-off of their answer
+   stages (it waits for the previous stage's event and records its own), while the copies, the
+   plan and the checksum of one egress slot overlap another slot's work.  A caller's own
+   emurx_tx_zmq_dev / emurx_tx_zmq_counted_dev calls must not overlap an egress batch.
+   INTEGRATION.md has the loop. */
+#define EMURX_EGRESS_SLOTS 2
+typedef struct emurx_egress_result {
+    const uint8_t* msgs;        /* ZMQ messages back to back, emurx_tx_zmq_dev's layout      */
+    const uint64_t* msg_off;    /* [n_msgs + 1] */
+    uint32_t n_msgs, n_frames;
+    uint64_t bytes;
+    const uint8_t* plan;        /* [n_frames] enum emurx_txp                                  */
+    const uint8_t* status;      /* [n_frames] EMURX_TX_OK / EMURX_TX_RANGE of the checksum call */
+    uint64_t plan_info[EMURX_TXP_INFO_WORDS];
+} emurx_egress_result;         /* 112 bytes */
+int emurx_egress_buffer(emurx_t* h, uint32_t slot, uint8_t** frames, emurx_desc** desc);
+int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags);
+int emurx_egress_wait(emurx_t* h, uint32_t slot, emurx_egress_result* res);
+
 /* ---- the stateless answers on the device ------------------------------------------------
    Three of the plugins' answers are a pure function of the frame and of a table the device
    holds; emurx_respond_dev builds them from a classified batch, shaped for emurx_tx_zmq_dev:

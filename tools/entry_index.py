@@ -50,6 +50,10 @@ GROUPS = [
      "(SURVEY §8e)"),
     ("Tx path", ["emurx_tx_checksum_dev", "emurx_tx_zmq_dev", "emurx_tx_zmq_counted_dev"],
      "gopacket checksum updates; `VethIFZmq.Send/FlushTx` `veth_zmq.go:149-200`"),
+    ("Tx planner and egress slots (tx from host memory)", ["emurx_tx_plan_dev", "emurx_egress_buffer", "emurx_egress_submit",
+                                                           "emurx_egress_wait"],
+     "the header walk of `ParsePacket` `parser.go:583-959` for the send paths' checksum calls (`tcp_output.go:64-76,110-112`, "
+     "`udp.go:143-156`, `icmp4.go:252-256`, `ipv6/mld.go:1271`); `Veth.Send` / `FlushTx` / `OnTick` `veth_zmq.go:149-200`"),
     ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev", "emurx_respond_ts_dev"],
      "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325` (echo and timestamp "
      "reply), `ipv6/ipv6.go:315-357`, `NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),

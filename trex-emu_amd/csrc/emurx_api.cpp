@@ -177,6 +177,39 @@ struct IngestSlot {
     }
 };
 
+// One in-flight batch of outgoing frames (emurx_egress_*): the caller's pinned frame area and
+// descriptors, their device copies, the chain's device outputs and the pinned result block that
+// k_egr_out writes.  Everything is sized once, by the slot's first emurx_egress_buffer, for
+// cfg.max_frames and cfg.max_bytes.
+struct EgressSlot {
+    hipStream_t st = nullptr;
+    hipEvent_t done = nullptr;
+    bool pending = false, submitted = false;
+    uint32_t n = 0;             // frames of the batch in flight / last waited for
+    uint64_t tx_cap = 0;        // its out_cap: 8 n + bytes
+    uint64_t cap = 0;           // message bytes the blocks hold: 8 max_frames + max_bytes, whole vectors
+    PinBuf<uint8_t> h_frames;   // written by the caller (+64 B pad)
+    PinBuf<emurx_desc> h_desc;  // written by the caller
+    DevBuf<uint8_t> d_frames, d_plan, d_status, d_tx;
+    DevBuf<emurx_desc> d_desc;
+    DevBuf<emurx_tx_desc> d_txd;
+    DevBuf<uint64_t> d_msg_off, d_info;  // d_info: the planner's info words, then the framing's two
+    PinBuf<uint8_t> h_res;               // the pinned result block
+    View<uint64_t> h_head, h_msg_off;
+    View<uint8_t> h_plan, h_status, h_tx;
+    void release() {
+        if (st) (void)hipStreamSynchronize(st);
+        h_frames.release(); h_desc.release(); h_res.release();
+        d_frames.release(); d_plan.release(); d_status.release(); d_tx.release(); d_desc.release(); d_txd.release();
+        d_msg_off.release(); d_info.release();
+        if (done) (void)hipEventDestroy(done);
+        if (st) (void)hipStreamDestroy(st);
+        done = nullptr;
+        st = nullptr;
+        pending = false;
+    }
+};
+
 // one staging slot of the table-delta ring: pinned entries, read by k_apply over the bus
 // (no copy launch: a delta is a few KiB)
 struct DeltaSlot {
@@ -260,6 +293,8 @@ struct emurx_ctx {
     // each stage waits for the previous one's event and records its own
     hipEvent_t ans_ev = nullptr;
     bool ans_recorded = false;
+    // egress slots (emurx_egress_*): their framing uses d_txz and joins the same hand-off
+    EgressSlot egr[EMURX_EGRESS_SLOTS];
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -1033,6 +1068,7 @@ void emurx_close(emurx_t* h) {
     emurx_comm_free(h->comm);
     h->comm = nullptr;
     for (auto& s : h->ing) s.release();
+    for (auto& s : h->egr) s.release();
     h->stage_fb.release();
     h->d_stage_fb.release();
     if (h->stage_ev) (void)hipEventDestroy(h->stage_ev);
@@ -2151,6 +2187,146 @@ int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out) {
     memcpy(out->rsp_info, hd, sizeof(out->rsp_info));
     memcpy(out->lrn_info, hd + EMURX_ANS_HEAD_LRN, sizeof(out->lrn_info));
     memcpy(out->nss_info, hd + EMURX_ANS_HEAD_NSS, sizeof(out->nss_info));
+    return EMURX_OK;
+}
+
+}  // extern "C"
+
+// ---- the tx planner and the egress slots ---------------------------------------------------------
+extern "C" {
+
+int emurx_tx_plan_dev(emurx_t* h, const uint8_t* d_frames, const emurx_desc* d_desc, uint32_t n, uint32_t flags,
+                      emurx_tx_desc* d_txdesc, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    if (!h || !d_info || (flags & ~EMURX_TXP_UDP0_KEEP) || (n && (!d_frames || !d_desc || !d_txdesc))) return EMURX_EINVAL;
+    if (((uintptr_t)d_desc & 7) || ((uintptr_t)d_txdesc & 15) || ((uintptr_t)d_info & 7)) return EMURX_EINVAL;
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;
+    int rc = bind(h);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = not_capturing(st))) return rc;
+    return emurx_launch_tx_plan(d_frames, d_desc, n, flags, d_txdesc, d_outcome, d_info, st) ? EMURX_EDEVICE : EMURX_OK;
+}
+
+int emurx_egress_buffer(emurx_t* h, uint32_t slot, uint8_t** frames, emurx_desc** desc) {
+    if (!h || !frames || !desc || slot >= EMURX_EGRESS_SLOTS) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    EgressSlot& s = h->egr[slot];
+    if (s.pending) return EMURX_EINVAL;
+    if (!s.h_res.p) {
+        // everything the chain needs, now: no submit allocates or synchronises for it.  The
+        // framing scratch may be in use by launches in flight, so the device is idle before it grows.
+        if (!EMURX_HIP_OK(hipDeviceSynchronize())) return EMURX_EDEVICE;
+        const uint32_t mf = std::min<uint32_t>(h->cfg.max_frames, EMURX_TX_ZMQ_MAX_FRAMES - 1);
+        const size_t mb = h->cfg.max_bytes;
+        if (!s.st && !EMURX_HIP_OK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking))) return EMURX_EDEVICE;
+        if (!s.done && !EMURX_HIP_OK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming))) return EMURX_EDEVICE;
+        if (!h->ans_ev && !EMURX_HIP_OK(hipEventCreateWithFlags(&h->ans_ev, hipEventDisableTiming))) return EMURX_EDEVICE;
+        if ((rc = txz_reserve(h, mf, h->stream))) return rc;
+        // the plain framing call's feedback words and event (emurx_tx_zmq_dev creates them on demand)
+        if (!h->txz_ev && (h->txz_fb.alloc(2) || !EMURX_HIP_OK(hipEventCreateWithFlags(&h->txz_ev, hipEventDisableTiming))))
+            return EMURX_ENOMEM;
+        const uint64_t cap = (8ull * mf + mb + 15) & ~15ull;
+        // device arrays with slack: frames are read as the aligned 16-byte blocks that hold them,
+        // and k_egr_out reads to the next 16-byte boundary past any count
+        if (s.h_frames.alloc(mb + 64) || s.h_desc.alloc((size_t)mf + 1) || s.d_frames.alloc(mb + 64) ||
+            s.d_desc.alloc((size_t)mf + 2) || s.d_txd.alloc((size_t)mf + 1) || s.d_plan.alloc((size_t)mf + 16) ||
+            s.d_status.alloc((size_t)mf + 16) || s.d_tx.alloc(cap + 16) || s.d_msg_off.alloc((size_t)mf + 3) ||
+            s.d_info.alloc(EMURX_EGR_HEAD_WORDS))
+            return EMURX_ENOMEM;
+        if (!EMURX_HIP_OK(hipMemset(s.d_info.p, 0, EMURX_EGR_HEAD_WORDS * sizeof(uint64_t)))) return EMURX_EDEVICE;
+        auto carve = [&](uint8_t* block) {
+            emurx_carver k(block);
+            s.h_head.p = k.take<uint64_t>(EMURX_EGR_HEAD_WORDS);
+            s.h_msg_off.p = k.take<uint64_t>((size_t)mf + 2);
+            s.h_plan.p = k.take<uint8_t>((size_t)mf + 16);
+            s.h_status.p = k.take<uint8_t>((size_t)mf + 16);
+            s.h_tx.p = k.take<uint8_t>(cap);
+            return k.bytes();
+        };
+        if (s.h_res.alloc(carve(nullptr))) return EMURX_ENOMEM;
+        carve(s.h_res.p);
+        memset(s.h_head.p, 0, EMURX_EGR_HEAD_WORDS * sizeof(uint64_t));
+        s.cap = cap;
+    }
+    *frames = s.h_frames.p;
+    *desc = s.h_desc.p;
+    return EMURX_OK;
+}
+
+int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags) {
+    if (!h || slot >= EMURX_EGRESS_SLOTS || (flags & ~EMURX_TXP_UDP0_KEEP)) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    EgressSlot& s = h->egr[slot];
+    if (s.pending || !s.h_res.p) return EMURX_EINVAL;  // in flight, or no emurx_egress_buffer yet
+    if (n > h->cfg.max_frames) return EMURX_ENOMEM;
+    if (bytes > h->cfg.max_bytes || n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
+    const emurx_desc* hd = s.h_desc.p;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((uint64_t)hd[i].off + hd[i].len > bytes) return EMURX_EINVAL;
+    hipStream_t st = s.st;
+    uint64_t* plan_info = s.d_info.p;
+    uint64_t* tx_info = s.d_info.p + EMURX_TXP_INFO_WORDS;
+    // 1. the frames and their descriptors; 2. the plan; 3. the checksums, in place
+    if (bytes && !EMURX_HIP_OK(hipMemcpyAsync(s.d_frames.p, s.h_frames.p, bytes, hipMemcpyHostToDevice, st))) return EMURX_EDEVICE;
+    if (n && !EMURX_HIP_OK(hipMemcpyAsync(s.d_desc.p, hd, (size_t)n * sizeof(emurx_desc), hipMemcpyHostToDevice, st)))
+        return EMURX_EDEVICE;
+    if (emurx_launch_tx_plan(s.d_frames.p, s.d_desc.p, n, flags, s.d_txd.p, s.d_plan.p, plan_info, st) ||
+        emurx_launch_tx_csum(s.d_frames.p, s.d_txd.p, n, s.d_status.p, st))
+        return EMURX_EDEVICE;
+    // 4. the framing, whose scratch is the handle's: behind the previous user's event, and the
+    // next one (an ingest slot's answer stages, another egress batch) waits for this one's
+    const uint64_t out_cap = 8ull * n + bytes;
+    if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
+    if ((rc = emurx_tx_zmq_dev(h, s.d_frames.p, s.d_desc.p, n, s.d_tx.p, out_cap, s.d_msg_off.p, tx_info, st))) return rc;
+    if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
+    h->ans_recorded = true;
+    // 5. what was produced, into the pinned result block
+    const emurx_egr_out a{reinterpret_cast<const unsigned long long*>(plan_info),
+                          reinterpret_cast<const unsigned long long*>(tx_info),
+                          s.d_tx.p,
+                          reinterpret_cast<const unsigned long long*>(s.d_msg_off.p),
+                          s.d_plan.p,
+                          s.d_status.p,
+                          reinterpret_cast<uint8_t*>(s.h_head.p),
+                          s.h_tx.p,
+                          reinterpret_cast<uint8_t*>(s.h_msg_off.p),
+                          s.h_plan.p,
+                          s.h_status.p,
+                          out_cap,
+                          n};
+    if (emurx_launch_egr_out(a, st) || !EMURX_HIP_OK(hipEventRecord(s.done, st))) return EMURX_EDEVICE;
+    s.n = n;
+    s.tx_cap = out_cap;
+    s.pending = true;
+    s.submitted = true;
+    return EMURX_OK;
+}
+
+int emurx_egress_wait(emurx_t* h, uint32_t slot, emurx_egress_result* res) {
+    if (!h || !res || slot >= EMURX_EGRESS_SLOTS) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    EgressSlot& s = h->egr[slot];
+    if (!s.submitted) return EMURX_EINVAL;
+    if (s.pending) {
+        if (!EMURX_HIP_OK(hipEventSynchronize(s.done))) return EMURX_EDEVICE;
+        s.pending = false;
+    }
+    const uint64_t* hd = s.h_head.p;
+    const uint64_t nmsg = hd[EMURX_TXP_INFO_WORDS], txb = hd[EMURX_TXP_INFO_WORDS + 1];
+    // the framing never needs more than 8 n + bytes for frames that do not overlap
+    if (nmsg > s.n || txb > s.tx_cap) return EMURX_ENOSPC;
+    memset(res, 0, sizeof(*res));
+    res->msgs = s.h_tx.p;
+    res->msg_off = s.h_msg_off.p;
+    res->n_msgs = (uint32_t)nmsg;
+    res->n_frames = s.n;
+    res->bytes = txb;
+    res->plan = s.h_plan.p;
+    res->status = s.h_status.p;
+    memcpy(res->plan_info, hd, sizeof(res->plan_info));
     return EMURX_OK;
 }
 

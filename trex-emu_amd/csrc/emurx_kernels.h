@@ -200,6 +200,27 @@ void emurx_comm_free(emurx_comm_state* c);   // emurx_comm.cpp: destroy a commun
 int emurx_launch_tx_csum(uint8_t* frames, const emurx_tx_desc* desc, uint32_t n, uint8_t* status,
                          hipStream_t st);
 
+// The tx planner (emurx_txplan.hip): see emurx_tx_plan_dev.  A clear of `info` and one launch;
+// outcome may be null.
+int emurx_launch_tx_plan(const uint8_t* frames, const emurx_desc* desc, uint32_t n, uint32_t flags, emurx_tx_desc* txd,
+                         uint8_t* outcome, uint64_t* info, hipStream_t st);
+// An egress slot's results to the host (k_egr_out, emurx_txplan.hip): the planner's info words and
+// the framing's {n_msgs, bytes} (device) become the head of the slot's pinned result block
+// (EMURX_EGR_HEAD_WORDS u64: plan info, framing info, zeros); msg_off[n_msgs + 1], the n plan and
+// status bytes and min(bytes, tx_cap) message bytes follow into their regions.  Every device array
+// readable to the next 16-byte boundary past its count.  One launch.
+enum { EMURX_EGR_HEAD_WORDS = EMURX_TXP_INFO_WORDS + 8 };
+struct emurx_egr_out {
+    const unsigned long long *plan_info, *tx_info;
+    const uint8_t* tx;
+    const unsigned long long* msg_off;
+    const uint8_t *plan, *status;
+    uint8_t *h_head, *h_tx, *h_msg_off, *h_plan, *h_status;  // pinned host
+    uint64_t tx_cap;
+    uint32_t n;
+};
+int emurx_launch_egr_out(const emurx_egr_out& a, hipStream_t st);
+
 // The device responder (emurx_respond.hip): see emurx_respond_dev / emurx_respond_kinds_dev /
 // emurx_respond_ts_dev.  kinds: EMURX_RSPK_*, EMURX_RSPK_TS among them; ip_time_ms: read for that
 // kind alone; info_words: 8 or EMURX_RSP_INFO_WORDS, the words of `info` that are written.

@@ -111,6 +111,11 @@ TX_L4_NONE, TX_L4_TCP4, TX_L4_UDP4, TX_L4_TCP6, TX_L4_UDP6, TX_L4_ICMP6, TX_L4_I
 TX_OK, TX_RANGE = 0, 1
 ZMQ_TX_BURST, ZMQ_TX_MAX_BUFFER, ZMQ_PKT_MAGIC = 64, 32768, 0xAA  # veth_zmq.go:36-37, :167
 TX_ZMQ_MAX_FRAMES = 1 << 26  # EMURX_TX_ZMQ_MAX_FRAMES: n of tx_zmq_dev / respond_dev is below it
+# enum emurx_txp: the per-frame outcome of emurx_tx_plan_dev; its d_info has TXP_INFO_WORDS words
+TXP_NONE, TXP_HDR, TXP_L4, TXP_LENGTH, TXP_BAD = range(5)
+TXP_UDP0_KEEP = 1  # EMURX_TXP_UDP0_KEEP: a UDP checksum field that is zero stays zero
+TXP_INFO_WORDS = 8
+EGRESS_SLOTS = 2   # EMURX_EGRESS_SLOTS
 # enum emurx_rsp: the per-frame outcome of emurx_respond_dev
 RSP_NONE, RSP_ARP, RSP_ICMP, RSP_ICMPV6, RSP_DROP_MCAST, RSP_HOST, RSP_NOSPC = range(7)
 RSP_ND = 7  # neighbour advertisement written (emurx_respond_kinds_dev with RSPK_ND)
@@ -235,6 +240,13 @@ class FlowsOut(C.Structure):
                 ("info", C.c_uint64 * FT_INFO_WORDS)]
 
 
+class EgressResult(C.Structure):
+    """emurx_egress_result: an egress slot's finished batch (emurx_egress_wait); pointers into library memory."""
+    _fields_ = [("msgs", C.c_void_p), ("msg_off", C.c_void_p), ("n_msgs", C.c_uint32), ("n_frames", C.c_uint32),
+                ("bytes", C.c_uint64), ("plan", C.c_void_p), ("status", C.c_void_p),
+                ("plan_info", C.c_uint64 * TXP_INFO_WORDS)]
+
+
 class DevOut(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("qlist", C.c_void_p), ("qcap", C.c_uint32),
                 ("tile_cnt", C.c_void_p), ("hist", C.c_void_p), ("flow", C.c_void_p)]
@@ -316,6 +328,10 @@ SIGNATURES = [
     ("emurx_tx_checksum_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     ("emurx_tx_zmq_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     ("emurx_tx_zmq_counted_dev", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P]),
+    ("emurx_tx_plan_dev", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    ("emurx_egress_buffer", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("emurx_egress_submit", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
+    ("emurx_egress_wait", C.c_int, [_P, C.c_uint32, C.POINTER(EgressResult)]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_ts_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P,
@@ -357,7 +373,8 @@ SIGNATURES = [
 OPTIONAL = {"emurx_last_uniform", "emurx_last_trim", "emurx_respond_ts_dev", "emurx_nsstat_ts_dev",
             "emurx_ingest_set_answers_ts", "emurx_ingest_set_time", "emurx_ping_max_events", "emurx_ping_dev",
             "emurx_ingest_set_ping", "emurx_ingest_set_now", "emurx_ingest_ping", "emurx_ftstat_max_events",
-            "emurx_ftstat_dev", "emurx_ingest_set_flows", "emurx_ingest_flows"}
+            "emurx_ftstat_dev", "emurx_ingest_set_flows", "emurx_ingest_flows", "emurx_tx_plan_dev", "emurx_egress_buffer",
+            "emurx_egress_submit", "emurx_egress_wait"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
 TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 
@@ -395,7 +412,7 @@ def source_id() -> str | None:
     """The id of the source tree (trex-emu_amd/Makefile SRC_ID: sha1 of the concatenated
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
-    src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip",
+    src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip", "emurx_txplan.hip",
            "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_ftstat.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]

@@ -358,6 +358,47 @@ class RxPath:
                                                            _addr(out), cap, _addr(msg_off), _addr(info),
                                                            _stream(stream)), "tx_zmq_counted_dev")
 
+    def tx_plan_dev(self, frames, desc, n: int, txdesc, outcome, info, flags: int = 0, stream=None):
+        """The TX_DESC_DTYPE descriptor of every frame, derived from the frame itself
+        (include/emu_rx.h emurx_tx_plan_dev): txdesc [n], outcome u8 [n] (abi.TXP_*, may be None),
+        info u64 [abi.TXP_INFO_WORDS]; flags abi.TXP_UDP0_KEEP."""
+        return abi.check(self.lib.emurx_tx_plan_dev(self.h, _addr(frames), _addr(desc), n, flags, _addr(txdesc),
+                                                    _addr(outcome), _addr(info), _stream(stream)), "tx_plan_dev")
+
+    # ---- egress slots: tx from host memory ------------------------------------------------
+    def egress_buffer(self, slot: int):
+        """The slot's pinned frame area (uint8 [cfg.max_bytes]) and descriptor array (abi.DESC_DTYPE
+        [cfg.max_frames]) as writable views (include/emu_rx.h emurx_egress_buffer)."""
+        f, d = C.c_void_p(), C.c_void_p()
+        abi.check(self.lib.emurx_egress_buffer(self.h, slot, C.byref(f), C.byref(d)), "egress_buffer")
+        mb, mf = int(self.cfg.max_bytes), int(self.cfg.max_frames)
+        frames = np.ctypeslib.as_array(C.cast(f, C.POINTER(C.c_uint8)), shape=(max(mb, 1),))[:mb]
+        desc = np.ctypeslib.as_array(C.cast(d, C.POINTER(C.c_uint8)), shape=(max(mf, 1) * 8,)).view(abi.DESC_DTYPE)[:mf]
+        return frames, desc
+
+    def egress_submit(self, slot: int, n: int, nbytes: int, flags: int = 0) -> None:
+        """Enqueue the slot's first n descriptors and nbytes of frames: plan, checksums, framing
+        (include/emu_rx.h emurx_egress_submit)."""
+        abi.check(self.lib.emurx_egress_submit(self.h, slot, n, nbytes, flags), "egress_submit")
+
+    def egress_wait(self, slot: int, copy: bool = True) -> dict:
+        """The slot's finished batch: msgs (the ZMQ messages back to back), msg_off u64 [n_msgs + 1],
+        plan and status u8 [n_frames], plan_info, n_msgs, n_frames, bytes (views into library
+        memory unless copy)."""
+        r = abi.EgressResult()
+        abi.check(self.lib.emurx_egress_wait(self.h, slot, C.byref(r)), "egress_wait")
+
+        def view(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            b = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dt).itemsize,))
+            v = b.view(dt)
+            return v.copy() if copy else v
+        n, m = int(r.n_frames), int(r.n_msgs)
+        return dict(msgs=view(r.msgs, int(r.bytes), np.uint8), msg_off=view(r.msg_off, m + 1, np.uint64),
+                    plan=view(r.plan, n, np.uint8), status=view(r.status, n, np.uint8),
+                    plan_info=np.array(r.plan_info, np.uint64), n_msgs=m, n_frames=n, bytes=int(r.bytes))
+
     def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None,
                     kinds=None, ip_time=None):
         """The ARP / ICMPv4 echo / ICMPv6 echo replies of a classified batch, built on the device
