@@ -690,6 +690,94 @@ int emurx_egress_buffer(emurx_t* h, uint32_t slot, uint8_t** frames, emurx_desc*
 int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags);
 int emurx_egress_wait(emurx_t* h, uint32_t slot, emurx_egress_result* res);
 
+/* ---- the send side of ping: resident templates -------------------------------------------------
+   Ping.sendPing (plugins/ping/ping.go:317-341) sends, per echo request, the packet that
+   PreparePingPacketTemplate built once (plugins/icmp/icmp.go:208-237, plugins/ipv6/ipv6.go:216-262)
+   with ten bytes changed: BE16 seq at icmp_off + 6, BE64 ts at icmp_off + 16 (one time.Now() per
+   call; seq increments per frame and wraps at 2^16), and the checksum at icmp_off + 2 through
+   UpdateChecksum2 / UpdateChecksum3 (gopacket layers/icmp4.go:238-285) on the live packet.  Frame
+   k of any such chain carries
+       cs = ~fold(~cs_t + ~seq_t + seq + sum over the four 16-bit words i of (~ts_t[i] + ts[i]))
+   all terms added as integers and folded once, cs_t, seq_t, ts_t the template's own fields: this
+   is also the full recompute over the patched frame, whenever the template's checksum field is
+   not 0xffff (UpdateChecksum and FixIcmpL4Checksum write none for a type 8 / 128 message; with it
+   the chain depends on its path).  So the templates live on the device and a sendPing call is one
+   16-byte request however many frames it bursts.
+   The store: emurx_pingtx_reserve(max_pings), once per handle, allocates it (EMURX_PINGTX_SLOT
+   device bytes per ping and a host shadow) and everything the calls below need: none of them
+   allocates.  A device slot is {u16 len, u16 icmp_off, u8 vport, 3 pad bytes} and the template's
+   bytes; len == 0 marks a free slot; the id is the slot index.  The host keeps the length per id,
+   so submit-time checks touch no template.
+     reserve  EMURX_EEXIST a second call; EMURX_ENOMEM a failed allocation; EMURX_EDEVICE a
+              host-only handle; EMURX_EINVAL max_pings == 0 or above 2^24.
+     add      EMURX_EINVAL: no reserve before it, a NULL pointer, icmp_off + 24 > len (the
+              timestamp must lie inside), len > EMURX_PINGTX_MAX_LEN (a large-payload ping stays on
+              the Go path), vport > 255, a checksum field of 0xffff; EMURX_ENOSPC: the store is
+              full.  *id = the lowest id that may be handed out.
+     remove   EMURX_ENOENT: a free or out-of-range id (or no reserve).
+   Edits are host calls that enqueue nothing.  They are shipped ahead of the next launch that reads
+   the store, on that launch's stream, behind the work of every stream that read it since the last
+   shipment; other streams wait for the shipment once, by event: the table shipment's rule
+   (emurx_classify_dev).  A removed id is not handed out again until every egress batch with
+   requests that was submitted before the remove has been waited for, so a batch in flight always
+   reads the template it was submitted with.  A caller of emurx_pingtx_dev on streams of its own
+   keeps that rule itself.  EMURX_PINGTX_SLOT bytes of device memory per reserved ping.
+   The shipment's two host waits: its four staging buffers hold 1,024 edited slots each, so a
+   launch behind more than 4,096 pending edits (a bulk add of 65,536 pings) waits on the host for
+   its own earlier k_ptx_apply launches while it ships; and the 17th distinct stream to read the
+   store since the last shipment drains the device once (hipDeviceSynchronize), as the table
+   shipment does.  A launch with no edit pending, or with up to 4,096, waits for nothing on the
+   host.  The library records an event on every stream that read the store since the last
+   shipment: a caller's stream must outlive the next launch that ships an edit (or emurx_close);
+   a destroyed one makes that launch fail with EMURX_EDEVICE. */
+#define EMURX_PINGTX_SLOT 256u      /* device bytes per template: 8-byte head + frame */
+#define EMURX_PINGTX_MAX_LEN 248u
+int emurx_pingtx_reserve(emurx_t* h, uint32_t max_pings);
+int emurx_pingtx_add(emurx_t* h, const uint8_t* tmpl, uint32_t len, uint32_t icmp_off,
+                     uint32_t vport, uint32_t* id);
+int emurx_pingtx_remove(emurx_t* h, uint32_t id);
+/* The generator.  Request r stands for `count` frames: frame k is the template of `id` with
+   seq + k (mod 2^16) and ts patched in and the checksum above.  The frames come out in request
+   order, then in k, in the responder's layout, so that emurx_tx_zmq_dev takes them: frame j at
+   d_out_desc[j].off, a multiple of 16 = the sum of align16(len) of the frames before it;
+   d_out_desc[j] = {off, len, vport, 0}; the bytes between a frame's end and the next 16-byte
+   boundary are unspecified; nothing is written at or past out_cap, nor at or past descriptor
+   desc_cap.  A request whose id is free or >= max_pings gets EMURX_PTX_BAD_ID and no frames;
+   count == 0 is EMURX_PTX_OK with no frames.  With too little room the whole requests that fit
+   are written, a prefix in request order, and every later request with frames gets
+   EMURX_PTX_NOSPC (so does one that would end past 4 GiB, the descriptor's offset range).
+   d_info (u64[EMURX_PTX_INFO_WORDS]) = {frames written, bytes needed, frames needed, requests with
+   outcome 0, 1, 2, 0, 0}; n_req == 0 writes a zero d_info.  d_outcome [n_req] may be NULL.
+   d_out 16-byte aligned, d_req, d_out_desc and d_info 8-byte.  EMURX_EINVAL: a NULL d_info, with
+   n_req > 0 a NULL d_req or d_out_desc, a NULL d_out with out_cap > 0, a misaligned array, a
+   capturing stream, no reserve; EMURX_ENOMEM: n_req > cfg.max_frames; EMURX_EDEVICE: a host-only
+   handle.  Three launches on `stream` (count, scan, emit: the emit deals 16-byte output chunks
+   over its lanes, so one request of 60,000 frames is as parallel as 60,000 requests of one), no
+   host synchronisation (but for the shipment's two cases above) and no allocation; the scratch is the handle's, handed from call to call
+   by event, so calls on different streams are safe and run one after the other. */
+typedef struct emurx_pingtx_req { uint32_t id; uint16_t seq; uint16_t count; uint64_t ts; } emurx_pingtx_req; /* 16 B */
+enum emurx_ptx { EMURX_PTX_OK = 0, EMURX_PTX_BAD_ID = 1, EMURX_PTX_NOSPC = 2 };
+#define EMURX_PTX_INFO_WORDS 8
+int emurx_pingtx_dev(emurx_t* h, const emurx_pingtx_req* d_req, uint32_t n_req,
+                     uint8_t* d_out, uint64_t out_cap, emurx_desc* d_out_desc, uint32_t desc_cap,
+                     uint8_t* d_outcome /* [n_req], may be NULL */, uint64_t* d_info, void* stream);
+/* On an egress slot.  emurx_egress_ping_buffer returns the slot's pinned request array
+   (cfg.max_frames entries; behind emurx_egress_buffer on the slot and emurx_pingtx_reserve, else
+   EMURX_EINVAL; the first call allocates it and its device copy).  emurx_egress_submit_ping is
+   emurx_egress_submit with n_req requests behind the n plain frames: the batch comes out as if the
+   caller had sent its n plain frames and then the requests' frames in request order, followed by
+   one FlushTx.  The submit reads each request once on the host against the per-id lengths, so the
+   sizes are exact: with G = the sum of count and B = the sum of count * align16(len), an id that is
+   free or out of range is EMURX_EINVAL, n + G > cfg.max_frames EMURX_ENOMEM, align16(bytes) + B >
+   cfg.max_bytes EMURX_ENOSPC; the other errors are emurx_egress_submit's; nothing is enqueued on
+   an error.  It enqueues the copies (now with 16 * n_req bytes of requests), the plan and the
+   checksum over the n plain frames only, the generator writing into the slot's device frame buffer
+   at align16(bytes) with its descriptors appended at index n, the framing over n + G frames, and
+   k_egr_out.  emurx_egress_wait is unchanged: n_frames = n + G, plan[i] / status[i] for i >= n are
+   EMURX_TXP_NONE / EMURX_TX_OK, plan_info counts the plain frames only. */
+int emurx_egress_ping_buffer(emurx_t* h, uint32_t slot, emurx_pingtx_req** req);
+int emurx_egress_submit_ping(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags, uint32_t n_req);
+
 /* ---- the stateless answers on the device ------------------------------------------------
    Three of the plugins' answers are a pure function of the frame and of a table the device
    holds; emurx_respond_dev builds them from a classified batch, shaped for emurx_tx_zmq_dev:

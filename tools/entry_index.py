@@ -54,6 +54,10 @@ GROUPS = [
                                                            "emurx_egress_wait"],
      "the header walk of `ParsePacket` `parser.go:583-959` for the send paths' checksum calls (`tcp_output.go:64-76,110-112`, "
      "`udp.go:143-156`, `icmp4.go:252-256`, `ipv6/mld.go:1271`); `Veth.Send` / `FlushTx` / `OnTick` `veth_zmq.go:149-200`"),
+    ("Send side of ping (resident templates)", ["emurx_pingtx_reserve", "emurx_pingtx_add", "emurx_pingtx_remove",
+                                                 "emurx_pingtx_dev", "emurx_egress_ping_buffer", "emurx_egress_submit_ping"],
+     "`Ping.sendPing` `ping/ping.go:317-341`, `PreparePingPacketTemplate` `icmp/icmp.go:208-237`, `ipv6/ipv6.go:216-262`, "
+     "`UpdateChecksum2` / `UpdateChecksum3` gopacket `layers/icmp4.go:238-285`; `NewPing` `ping/ping.go:185-210`, `OnRemove` `:219-224`"),
     ("Device responder", ["emurx_respond_dev", "emurx_respond_kinds_dev", "emurx_respond_ts_dev"],
      "`PluginArpClient.Respond` `arp/arp.go:776-790`, `HandleEcho` `icmp/icmp.go:289-325` (echo and timestamp "
      "reply), `ipv6/ipv6.go:315-357`, `NdClientCtx.Respond` `ipv6/nd.go:1220-1253`"),

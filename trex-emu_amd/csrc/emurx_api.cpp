@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -197,8 +198,14 @@ struct EgressSlot {
     PinBuf<uint8_t> h_res;               // the pinned result block
     View<uint64_t> h_head, h_msg_off;
     View<uint8_t> h_plan, h_status, h_tx;
+    // echo requests behind the plain frames (emurx_egress_ping_buffer / _submit_ping)
+    PinBuf<emurx_pingtx_req> h_req;      // written by the caller
+    DevBuf<emurx_pingtx_req> d_req;
+    DevBuf<uint64_t> d_pinfo;            // the generator's info words (the submit's sizes are exact: not read)
+    uint64_t ping_seq = 0, ping_done = 0;  // batches with requests submitted / waited for (PingTx::limbo)
     void release() {
         if (st) (void)hipStreamSynchronize(st);
+        h_req.release(); d_req.release(); d_pinfo.release();
         h_frames.release(); h_desc.release(); h_res.release();
         d_frames.release(); d_plan.release(); d_status.release(); d_tx.release(); d_desc.release(); d_txd.release();
         d_msg_off.release(); d_info.release();
@@ -219,6 +226,61 @@ struct DeltaSlot {
 };
 constexpr int kDeltaRing = 4;
 constexpr size_t kMaxReaders = 16;
+
+// The resident ping templates (emurx_pingtx_*).  The shadow is the host's truth; an edit marks its
+// id, and the marked slots travel ahead of the next launch that reads the store (ship_pingtx) as
+// 272-byte entries in a ring of pinned buffers that one k_ptx_apply launch reads directly, like the
+// table deltas.  Everything is sized by emurx_pingtx_reserve: the vectors below never grow.
+struct PingTx {
+    static constexpr uint32_t kEntry = 16 + EMURX_PINGTX_SLOT;  // {id, zeros}, the slot
+    uint32_t max = 0;                    // 0: not reserved
+    DevBuf<uint8_t> d_store;             // max slots + 16 bytes (a slot's last chunk is read whole)
+    std::vector<uint8_t> shadow;         // max slots
+    std::vector<uint16_t> len;           // per id, 0: free
+    std::vector<uint8_t> marked;         // per id: in `dirty`
+    std::vector<uint32_t> dirty;         // ids edited since the last shipment
+    std::vector<uint32_t> free_ids;      // min-heap of the ids that may be handed out
+    // removed ids wait here, in removal order, until every egress batch with requests that was
+    // submitted before the remove has been waited for: seq = the slots' ping_seq at the remove
+    struct Limbo {
+        uint32_t id;
+        uint64_t seq[EMURX_EGRESS_SLOTS];
+    };
+    std::vector<Limbo> limbo;            // ring of max entries
+    uint32_t limbo_head = 0, limbo_n = 0;
+    // the shipment: staging ring, the streams that read the store since the last shipment, and
+    // which shipment every stream has waited for (the table shipment's bookkeeping)
+    uint32_t stage_cap = 0;              // entries per staging buffer
+    PinBuf<uint8_t> stage[kDeltaRing];
+    hipEvent_t stage_ev[kDeltaRing] = {};
+    bool stage_used[kDeltaRing] = {};
+    uint32_t stage_i = 0;
+    hipEvent_t ship_ev = nullptr, reader_ev[kMaxReaders] = {};
+    uint64_t ship_gen = 0;
+    std::vector<hipStream_t> readers;
+    std::vector<std::pair<hipStream_t, uint64_t>> waited;
+    // the generator's scratch, sized for cfg.max_frames requests, handed from call to call by event
+    DevBuf<uint8_t> d_scratch;
+    hipEvent_t scr_ev = nullptr;
+    bool scr_recorded = false;
+    void release() {
+        d_store.release();
+        d_scratch.release();
+        for (int k = 0; k < kDeltaRing; ++k) {
+            stage[k].release();
+            if (stage_ev[k]) (void)hipEventDestroy(stage_ev[k]);
+            stage_ev[k] = nullptr;
+        }
+        for (auto& e : reader_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        if (ship_ev) (void)hipEventDestroy(ship_ev);
+        if (scr_ev) (void)hipEventDestroy(scr_ev);
+        ship_ev = scr_ev = nullptr;
+        max = 0;
+    }
+};
 
 }  // namespace
 
@@ -295,6 +357,8 @@ struct emurx_ctx {
     bool ans_recorded = false;
     // egress slots (emurx_egress_*): their framing uses d_txz and joins the same hand-off
     EgressSlot egr[EMURX_EGRESS_SLOTS];
+    // the resident ping templates and their generator (emurx_pingtx_*)
+    PingTx ptx;
 
     // Namespace-partition packing scratch (emurx_route_dev / emurx_classify_route_dev /
     // emurx_parse_route_dev): one set per stream, so routes of batches pipelined over several
@@ -1069,6 +1133,7 @@ void emurx_close(emurx_t* h) {
     h->comm = nullptr;
     for (auto& s : h->ing) s.release();
     for (auto& s : h->egr) s.release();
+    h->ptx.release();
     h->stage_fb.release();
     h->d_stage_fb.release();
     if (h->stage_ev) (void)hipEventDestroy(h->stage_ev);
@@ -2192,6 +2257,206 @@ int emurx_ingest_answers(emurx_t* h, uint32_t slot, emurx_answers* out) {
 
 }  // extern "C"
 
+// ---- the resident ping templates and their generator (emurx_pingtx_*) ---------------------------
+namespace {
+
+// Ship the edited template slots on `st`: behind every stream that read the store since the last
+// shipment, ahead of every later reader (ship_tables' rule, with the store's own bookkeeping).
+// The staging buffers hold stage_cap slots each; more edits take several of them, and a buffer
+// still in use by an earlier k_ptx_apply is waited for on the host.
+int ship_pingtx(emurx_t* h, hipStream_t st) {
+    PingTx& x = h->ptx;
+    for (size_t k = 0; k < x.readers.size(); ++k) {
+        if (x.readers[k] == st) continue;
+        if (!EMURX_HIP_OK(hipEventRecord(x.reader_ev[k], x.readers[k])) ||
+            !EMURX_HIP_OK(hipStreamWaitEvent(st, x.reader_ev[k], 0)))
+            return EMURX_EDEVICE;
+    }
+    for (size_t at = 0; at < x.dirty.size(); at += x.stage_cap) {
+        const uint32_t k = x.stage_i++ % kDeltaRing;
+        if (x.stage_used[k] && !EMURX_HIP_OK(hipEventSynchronize(x.stage_ev[k]))) return EMURX_EDEVICE;
+        const uint32_t cnt = (uint32_t)std::min<size_t>(x.stage_cap, x.dirty.size() - at);
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint32_t id = x.dirty[at + j];
+            uint8_t* e = x.stage[k].p + (size_t)j * PingTx::kEntry;
+            memset(e, 0, 16);
+            memcpy(e, &id, 4);
+            memcpy(e + 16, &x.shadow[(size_t)id * EMURX_PINGTX_SLOT], EMURX_PINGTX_SLOT);
+            x.marked[id] = 0;
+        }
+        if (emurx_launch_pingtx_apply(x.stage[k].p, cnt, x.d_store.p, st) || !EMURX_HIP_OK(hipEventRecord(x.stage_ev[k], st)))
+            return EMURX_EDEVICE;
+        x.stage_used[k] = true;
+    }
+    x.dirty.clear();
+    if (!EMURX_HIP_OK(hipEventRecord(x.ship_ev, st))) return EMURX_EDEVICE;
+    ++x.ship_gen;
+    x.readers.clear();
+    return EMURX_OK;
+}
+
+// Before a launch on `st` that reads the store: ship pending edits, or wait for the last shipment
+// if this stream has not yet; remember st as a reader for the next shipment.
+int pingtx_prepare_read(emurx_t* h, hipStream_t st) {
+    PingTx& x = h->ptx;
+    int rc;
+    uint64_t* w = nullptr;
+    for (auto& e : x.waited)
+        if (e.first == st) w = &e.second;
+    if (!w) {
+        if (x.waited.size() >= 4 * kMaxReaders) x.waited.clear();  // forgotten streams wait again: harmless
+        x.waited.emplace_back(st, 0);  // within the capacity emurx_pingtx_reserve set
+        w = &x.waited.back().second;
+    }
+    if (!x.dirty.empty()) {
+        if ((rc = ship_pingtx(h, st))) return rc;
+    } else if (*w < x.ship_gen) {
+        if (!EMURX_HIP_OK(hipStreamWaitEvent(st, x.ship_ev, 0))) return EMURX_EDEVICE;
+    }
+    *w = x.ship_gen;
+    if (std::find(x.readers.begin(), x.readers.end(), st) == x.readers.end()) {
+        if (x.readers.size() >= kMaxReaders) {  // many distinct streams: drain them all once
+            if (!EMURX_HIP_OK(hipDeviceSynchronize())) return EMURX_EDEVICE;
+            x.readers.clear();
+        }
+        x.readers.push_back(st);
+    }
+    return EMURX_OK;
+}
+
+// one generator call on st: behind the store's shipment and the scratch's previous user
+int pingtx_run(emurx_t* h, const emurx_pingtx_req* d_req, uint32_t n_req, uint8_t* d_out, uint64_t out_cap,
+               emurx_desc* d_out_desc, uint32_t desc_cap, uint32_t off_base, uint8_t* fzero0, uint8_t* fzero1,
+               uint8_t* d_outcome, uint64_t* d_info, hipStream_t st) {
+    PingTx& x = h->ptx;
+    int rc;
+    if ((rc = pingtx_prepare_read(h, st))) return rc;
+    if (x.scr_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, x.scr_ev, 0))) return EMURX_EDEVICE;
+    if (emurx_launch_pingtx(d_req, n_req, x.d_store.p, x.max, d_out, out_cap, d_out_desc, desc_cap, off_base, fzero0, fzero1,
+                            d_outcome, d_info, x.d_scratch.p, st) ||
+        !EMURX_HIP_OK(hipEventRecord(x.scr_ev, st)))
+        return EMURX_EDEVICE;
+    x.scr_recorded = true;
+    return EMURX_OK;
+}
+
+void pingtx_mark(PingTx& x, uint32_t id) {
+    if (x.marked[id]) return;
+    x.marked[id] = 1;
+    x.dirty.push_back(id);  // at most one entry per id: within the reserved capacity
+}
+
+}  // namespace
+
+extern "C" {
+
+int emurx_pingtx_reserve(emurx_t* h, uint32_t max_pings) {
+    if (!h || max_pings == 0 || max_pings > (1u << 24)) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    PingTx& x = h->ptx;
+    if (x.max) return EMURX_EEXIST;
+    const size_t bytes = (size_t)max_pings * EMURX_PINGTX_SLOT;
+    auto fail = [&](int code) {
+        x.release();
+        return code;
+    };
+    try {
+        x.shadow.assign(bytes, 0);
+        x.len.assign(max_pings, 0);
+        x.marked.assign(max_pings, 0);
+        x.dirty.clear();
+        x.dirty.reserve(max_pings);
+        x.free_ids.resize(max_pings);
+        for (uint32_t i = 0; i < max_pings; ++i) x.free_ids[i] = i;  // ascending: a min-heap as it stands
+        x.limbo.assign(max_pings, PingTx::Limbo{});
+        x.readers.reserve(kMaxReaders);
+        x.waited.reserve(4 * kMaxReaders);
+    } catch (...) {  // bad_alloc, length_error: no exception crosses the ABI
+        return fail(EMURX_ENOMEM);
+    }
+    x.limbo_head = x.limbo_n = 0;
+    x.stage_cap = std::min<uint32_t>(max_pings, 1024);
+    if (x.d_store.alloc(bytes + 16) || x.d_scratch.alloc(emurx_ptx_scratch_bytes(h->cfg.max_frames))) return fail(EMURX_ENOMEM);
+    for (int k = 0; k < kDeltaRing; ++k) {
+        if (x.stage[k].alloc((size_t)x.stage_cap * PingTx::kEntry)) return fail(EMURX_ENOMEM);
+        if (!EMURX_HIP_OK(hipEventCreateWithFlags(&x.stage_ev[k], hipEventDisableTiming))) return fail(EMURX_EDEVICE);
+        x.stage_used[k] = false;
+    }
+    for (auto& e : x.reader_ev)
+        if (!EMURX_HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming))) return fail(EMURX_EDEVICE);
+    if (!EMURX_HIP_OK(hipEventCreateWithFlags(&x.ship_ev, hipEventDisableTiming)) ||
+        !EMURX_HIP_OK(hipEventCreateWithFlags(&x.scr_ev, hipEventDisableTiming)) ||
+        !EMURX_HIP_OK(hipMemset(x.d_store.p, 0, bytes + 16)))  // every slot free
+        return fail(EMURX_EDEVICE);
+    x.scr_recorded = false;
+    x.ship_gen = 0;
+    x.max = max_pings;
+    return EMURX_OK;
+}
+
+int emurx_pingtx_add(emurx_t* h, const uint8_t* tmpl, uint32_t len, uint32_t icmp_off, uint32_t vport, uint32_t* id) {
+    if (!h || !tmpl || !id) return EMURX_EINVAL;
+    PingTx& x = h->ptx;
+    if (!x.max || len > EMURX_PINGTX_MAX_LEN || icmp_off > len || icmp_off + 24 > len || vport > 255) return EMURX_EINVAL;
+    if (be16(tmpl + icmp_off + 2) == 0xffff) return EMURX_EINVAL;  // the chain depends on its path there
+    // the removed ids whose last readers have been waited for may be handed out again
+    while (x.limbo_n) {
+        const PingTx::Limbo& l = x.limbo[x.limbo_head];
+        bool ready = true;
+        for (int k = 0; k < EMURX_EGRESS_SLOTS; ++k) ready = ready && h->egr[k].ping_done >= l.seq[k];
+        if (!ready) break;
+        x.free_ids.push_back(l.id);  // within the capacity: an id is in one place at a time
+        std::push_heap(x.free_ids.begin(), x.free_ids.end(), std::greater<uint32_t>());
+        x.limbo_head = (x.limbo_head + 1) % x.max;
+        --x.limbo_n;
+    }
+    if (x.free_ids.empty()) return EMURX_ENOSPC;
+    std::pop_heap(x.free_ids.begin(), x.free_ids.end(), std::greater<uint32_t>());
+    const uint32_t i = x.free_ids.back();
+    x.free_ids.pop_back();
+    uint8_t* s = &x.shadow[(size_t)i * EMURX_PINGTX_SLOT];
+    memset(s, 0, EMURX_PINGTX_SLOT);
+    const uint16_t l16 = (uint16_t)len, o16 = (uint16_t)icmp_off;
+    memcpy(s, &l16, 2);
+    memcpy(s + 2, &o16, 2);
+    s[4] = (uint8_t)vport;
+    memcpy(s + 8, tmpl, len);
+    x.len[i] = l16;
+    pingtx_mark(x, i);
+    *id = i;
+    return EMURX_OK;
+}
+
+int emurx_pingtx_remove(emurx_t* h, uint32_t id) {
+    if (!h) return EMURX_EINVAL;
+    PingTx& x = h->ptx;
+    if (id >= x.max || !x.len[id]) return EMURX_ENOENT;
+    x.len[id] = 0;
+    memset(&x.shadow[(size_t)id * EMURX_PINGTX_SLOT], 0, 8);  // len 0: free
+    pingtx_mark(x, id);
+    PingTx::Limbo& l = x.limbo[(x.limbo_head + x.limbo_n++) % x.max];
+    l.id = id;
+    for (int k = 0; k < EMURX_EGRESS_SLOTS; ++k) l.seq[k] = h->egr[k].ping_seq;
+    return EMURX_OK;
+}
+
+int emurx_pingtx_dev(emurx_t* h, const emurx_pingtx_req* d_req, uint32_t n_req, uint8_t* d_out, uint64_t out_cap,
+                     emurx_desc* d_out_desc, uint32_t desc_cap, uint8_t* d_outcome, uint64_t* d_info, void* stream) {
+    if (!h || !d_info || (n_req && (!d_req || !d_out_desc || (!d_out && out_cap)))) return EMURX_EINVAL;
+    if (((uintptr_t)d_out & 15) || ((uintptr_t)d_req & 7) || ((uintptr_t)d_out_desc & 7) || ((uintptr_t)d_info & 7))
+        return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    if (!h->ptx.max) return EMURX_EINVAL;
+    if (n_req > h->cfg.max_frames) return EMURX_ENOMEM;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = not_capturing(st))) return rc;
+    return pingtx_run(h, d_req, n_req, d_out, out_cap, d_out_desc, desc_cap, 0, nullptr, nullptr, d_outcome, d_info, st);
+}
+
+}  // extern "C"
+
 // ---- the tx planner and the egress slots ---------------------------------------------------------
 extern "C" {
 
@@ -2254,32 +2519,59 @@ int emurx_egress_buffer(emurx_t* h, uint32_t slot, uint8_t** frames, emurx_desc*
     return EMURX_OK;
 }
 
-int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags) {
+// emurx_egress_submit and emurx_egress_submit_ping: n plain frames, then the frames of n_req echo
+// requests (none: the plain submit, enqueue for enqueue)
+static int egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags, uint32_t n_req) {
     if (!h || slot >= EMURX_EGRESS_SLOTS || (flags & ~EMURX_TXP_UDP0_KEEP)) return EMURX_EINVAL;
     int rc = bind(h);
     if (rc) return rc;
     EgressSlot& s = h->egr[slot];
     if (s.pending || !s.h_res.p) return EMURX_EINVAL;  // in flight, or no emurx_egress_buffer yet
-    if (n > h->cfg.max_frames) return EMURX_ENOMEM;
+    if (n_req && !s.h_req.p) return EMURX_EINVAL;      // no emurx_egress_ping_buffer yet
+    if (n > h->cfg.max_frames || n_req > h->cfg.max_frames) return EMURX_ENOMEM;
     if (bytes > h->cfg.max_bytes || n >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
     const emurx_desc* hd = s.h_desc.p;
     for (uint32_t i = 0; i < n; ++i)
         if ((uint64_t)hd[i].off + hd[i].len > bytes) return EMURX_EINVAL;
+    // the requests against the per-id lengths: G frames and B bytes, exact
+    uint64_t G = 0, B = 0;
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const emurx_pingtx_req& q = s.h_req.p[r];
+        if (q.id >= h->ptx.max || !h->ptx.len[q.id]) return EMURX_EINVAL;
+        G += q.count;
+        B += (uint64_t)q.count * ((h->ptx.len[q.id] + 15u) & ~15u);
+    }
+    const uint64_t gen_at = (bytes + 15) & ~15ull;  // the generated frames' place in the frame area
+    if (n + G > h->cfg.max_frames) return EMURX_ENOMEM;
+    if (n_req && gen_at + B > h->cfg.max_bytes) return EMURX_ENOSPC;
+    if (n + G >= EMURX_TX_ZMQ_MAX_FRAMES) return EMURX_ENOSPC;
+    const uint32_t nf = n + (uint32_t)G;
     hipStream_t st = s.st;
     uint64_t* plan_info = s.d_info.p;
     uint64_t* tx_info = s.d_info.p + EMURX_TXP_INFO_WORDS;
-    // 1. the frames and their descriptors; 2. the plan; 3. the checksums, in place
+    // 1. the frames, their descriptors and the requests; 2. the plan; 3. the checksums, in place
     if (bytes && !EMURX_HIP_OK(hipMemcpyAsync(s.d_frames.p, s.h_frames.p, bytes, hipMemcpyHostToDevice, st))) return EMURX_EDEVICE;
     if (n && !EMURX_HIP_OK(hipMemcpyAsync(s.d_desc.p, hd, (size_t)n * sizeof(emurx_desc), hipMemcpyHostToDevice, st)))
+        return EMURX_EDEVICE;
+    if (n_req && !EMURX_HIP_OK(hipMemcpyAsync(s.d_req.p, s.h_req.p, (size_t)n_req * sizeof(emurx_pingtx_req),
+                                              hipMemcpyHostToDevice, st)))
         return EMURX_EDEVICE;
     if (emurx_launch_tx_plan(s.d_frames.p, s.d_desc.p, n, flags, s.d_txd.p, s.d_plan.p, plan_info, st) ||
         emurx_launch_tx_csum(s.d_frames.p, s.d_txd.p, n, s.d_status.p, st))
         return EMURX_EDEVICE;
+    if (n_req) {
+        // the generated frames behind the plain ones, their descriptors from index n on; they are
+        // finished as they are written: the generator gives each EMURX_TXP_NONE / EMURX_TX_OK
+        if ((rc = pingtx_run(h, s.d_req.p, n_req, s.d_frames.p + gen_at, B, s.d_desc.p + n, (uint32_t)G, (uint32_t)gen_at,
+                             s.d_plan.p + n, s.d_status.p + n, nullptr, s.d_pinfo.p, st)))
+            return rc;
+        ++s.ping_seq;
+    }
     // 4. the framing, whose scratch is the handle's: behind the previous user's event, and the
     // next one (an ingest slot's answer stages, another egress batch) waits for this one's
-    const uint64_t out_cap = 8ull * n + bytes;
+    const uint64_t out_cap = 8ull * nf + bytes + B;
     if (h->ans_recorded && !EMURX_HIP_OK(hipStreamWaitEvent(st, h->ans_ev, 0))) return EMURX_EDEVICE;
-    if ((rc = emurx_tx_zmq_dev(h, s.d_frames.p, s.d_desc.p, n, s.d_tx.p, out_cap, s.d_msg_off.p, tx_info, st))) return rc;
+    if ((rc = emurx_tx_zmq_dev(h, s.d_frames.p, s.d_desc.p, nf, s.d_tx.p, out_cap, s.d_msg_off.p, tx_info, st))) return rc;
     if (!EMURX_HIP_OK(hipEventRecord(h->ans_ev, st))) return EMURX_EDEVICE;
     h->ans_recorded = true;
     // 5. what was produced, into the pinned result block
@@ -2295,13 +2587,35 @@ int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, u
                           s.h_plan.p,
                           s.h_status.p,
                           out_cap,
-                          n};
+                          nf};
     if (emurx_launch_egr_out(a, st) || !EMURX_HIP_OK(hipEventRecord(s.done, st))) return EMURX_EDEVICE;
-    s.n = n;
+    s.n = nf;
     s.tx_cap = out_cap;
     s.pending = true;
     s.submitted = true;
     return EMURX_OK;
+}
+
+int emurx_egress_submit(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags) {
+    return egress_submit(h, slot, n, bytes, flags, 0);
+}
+
+int emurx_egress_ping_buffer(emurx_t* h, uint32_t slot, emurx_pingtx_req** req) {
+    if (!h || !req || slot >= EMURX_EGRESS_SLOTS) return EMURX_EINVAL;
+    int rc = bind(h);
+    if (rc) return rc;
+    EgressSlot& s = h->egr[slot];
+    if (s.pending || !s.h_res.p || !h->ptx.max) return EMURX_EINVAL;
+    if (!s.h_req.p) {
+        const size_t mf = std::max<size_t>(h->cfg.max_frames, 1);
+        if (s.h_req.alloc(mf) || s.d_req.alloc(mf) || s.d_pinfo.alloc(EMURX_PTX_INFO_WORDS)) return EMURX_ENOMEM;
+    }
+    *req = s.h_req.p;
+    return EMURX_OK;
+}
+
+int emurx_egress_submit_ping(emurx_t* h, uint32_t slot, uint32_t n, uint64_t bytes, uint32_t flags, uint32_t n_req) {
+    return egress_submit(h, slot, n, bytes, flags, n_req);
 }
 
 int emurx_egress_wait(emurx_t* h, uint32_t slot, emurx_egress_result* res) {
@@ -2313,6 +2627,7 @@ int emurx_egress_wait(emurx_t* h, uint32_t slot, emurx_egress_result* res) {
     if (s.pending) {
         if (!EMURX_HIP_OK(hipEventSynchronize(s.done))) return EMURX_EDEVICE;
         s.pending = false;
+        s.ping_done = s.ping_seq;  // removed template ids this batch may have read can be handed out again
     }
     const uint64_t* hd = s.h_head.p;
     const uint64_t nmsg = hd[EMURX_TXP_INFO_WORDS], txb = hd[EMURX_TXP_INFO_WORDS + 1];

@@ -221,6 +221,20 @@ struct emurx_egr_out {
 };
 int emurx_launch_egr_out(const emurx_egr_out& a, hipStream_t st);
 
+// The echo-request generator (emurx_pingtx.hip): see emurx_pingtx_dev.  store: the template store's
+// device image, max_pings slots of EMURX_PINGTX_SLOT bytes readable 16 bytes past its end; scratch:
+// emurx_ptx_scratch_bytes(n), no initial state.  off_base (a multiple of 16): added to every
+// descriptor's offset, for an `out` that lies inside a larger frame buffer.  fzero0, fzero1 (both or
+// neither, desc_cap bytes each): a zero byte per written frame, at the frame's index (an egress
+// slot's plan and status bytes).  Three launches.  emurx_launch_pingtx_apply copies
+// n edited slots into the store: delta holds 272 bytes per slot, {u32 id, 12 zero bytes} and the
+// slot's bytes, read where they lie (pinned host memory); ids below max_pings.  One launch.
+size_t emurx_ptx_scratch_bytes(uint32_t n);
+int emurx_launch_pingtx(const emurx_pingtx_req* req, uint32_t n, const uint8_t* store, uint32_t max_pings, uint8_t* out,
+                        uint64_t cap, emurx_desc* out_desc, uint32_t desc_cap, uint32_t off_base, uint8_t* fzero0,
+                        uint8_t* fzero1, uint8_t* outcome, uint64_t* info, void* scratch, hipStream_t st);
+int emurx_launch_pingtx_apply(const void* delta, uint32_t n, uint8_t* store, hipStream_t st);
+
 // The device responder (emurx_respond.hip): see emurx_respond_dev / emurx_respond_kinds_dev /
 // emurx_respond_ts_dev.  kinds: EMURX_RSPK_*, EMURX_RSPK_TS among them; ip_time_ms: read for that
 // kind alone; info_words: 8 or EMURX_RSP_INFO_WORDS, the words of `info` that are written.

@@ -116,6 +116,14 @@ TXP_NONE, TXP_HDR, TXP_L4, TXP_LENGTH, TXP_BAD = range(5)
 TXP_UDP0_KEEP = 1  # EMURX_TXP_UDP0_KEEP: a UDP checksum field that is zero stays zero
 TXP_INFO_WORDS = 8
 EGRESS_SLOTS = 2   # EMURX_EGRESS_SLOTS
+# the resident ping templates (emurx_pingtx_*): device bytes per template, the longest template
+PINGTX_SLOT, PINGTX_MAX_LEN = 256, 248
+# enum emurx_ptx: the per-request outcome of emurx_pingtx_dev; its d_info has PTX_INFO_WORDS words
+PTX_OK, PTX_BAD_ID, PTX_NOSPC = range(3)
+PTX_INFO_WORDS = 8
+# emurx_pingtx_req: `count` echo requests from template `id`, sequence numbers seq, seq + 1, ...
+PINGTX_REQ_DTYPE = np.dtype([("id", "<u4"), ("seq", "<u2"), ("count", "<u2"), ("ts", "<u8")])
+assert PINGTX_REQ_DTYPE.itemsize == 16
 # enum emurx_rsp: the per-frame outcome of emurx_respond_dev
 RSP_NONE, RSP_ARP, RSP_ICMP, RSP_ICMPV6, RSP_DROP_MCAST, RSP_HOST, RSP_NOSPC = range(7)
 RSP_ND = 7  # neighbour advertisement written (emurx_respond_kinds_dev with RSPK_ND)
@@ -332,6 +340,12 @@ SIGNATURES = [
     ("emurx_egress_buffer", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("emurx_egress_submit", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     ("emurx_egress_wait", C.c_int, [_P, C.c_uint32, C.POINTER(EgressResult)]),
+    ("emurx_pingtx_reserve", C.c_int, [_P, C.c_uint32]),
+    ("emurx_pingtx_add", C.c_int, [_P, _U8P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("emurx_pingtx_remove", C.c_int, [_P, C.c_uint32]),
+    ("emurx_pingtx_dev", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P]),
+    ("emurx_egress_ping_buffer", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("emurx_egress_submit_ping", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]),
     ("emurx_respond_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_kinds_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     ("emurx_respond_ts_dev", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P,
@@ -374,7 +388,8 @@ OPTIONAL = {"emurx_last_uniform", "emurx_last_trim", "emurx_respond_ts_dev", "em
             "emurx_ingest_set_answers_ts", "emurx_ingest_set_time", "emurx_ping_max_events", "emurx_ping_dev",
             "emurx_ingest_set_ping", "emurx_ingest_set_now", "emurx_ingest_ping", "emurx_ftstat_max_events",
             "emurx_ftstat_dev", "emurx_ingest_set_flows", "emurx_ingest_flows", "emurx_tx_plan_dev", "emurx_egress_buffer",
-            "emurx_egress_submit", "emurx_egress_wait"}
+            "emurx_egress_submit", "emurx_egress_wait", "emurx_pingtx_reserve", "emurx_pingtx_add", "emurx_pingtx_remove",
+            "emurx_pingtx_dev", "emurx_egress_ping_buffer", "emurx_egress_submit_ping"}
 UNI_WORDS, UNI_PARSE, UNI_LOOKUP, UNI_SAMPLED = 256, 1, 2, 4  # EMURX_UNI_* (emurx_last_uniform)
 TRIM_RANGE = 1  # EMURX_TRIM_RANGE (emurx_last_trim)
 
@@ -413,7 +428,7 @@ def source_id() -> str | None:
     sources, headers and Makefile, first 16 hex digits); None when a file is missing."""
     import hashlib
     src = ["emurx_kernels.hip", "emurx_route.hip", "emurx_ingest.hip", "emurx_tx.hip", "emurx_txzmq.hip", "emurx_txplan.hip",
-           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_ftstat.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
+           "emurx_respond.hip", "emurx_learn.hip", "emurx_nsstat.hip", "emurx_ping.hip", "emurx_ftstat.hip", "emurx_pingtx.hip", "emurx_api.cpp", "emurx_mirror.cpp", "emurx_comm.cpp"]
     hdr = ["emurx_kernels.h", "emurx_tables.h", "emurx_wave.h", "emurx_parse.h", "emurx_mirror.h", "emurx_rsp_dev.h"]
     files = [PKG_ROOT / "csrc" / f for f in src + hdr] + [REPO_ROOT / "include" / "emu_rx.h", PKG_ROOT / "Makefile"]
     h = hashlib.sha1()

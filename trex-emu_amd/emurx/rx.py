@@ -399,6 +399,42 @@ class RxPath:
                     plan=view(r.plan, n, np.uint8), status=view(r.status, n, np.uint8),
                     plan_info=np.array(r.plan_info, np.uint64), n_msgs=m, n_frames=n, bytes=int(r.bytes))
 
+    # ---- the send side of ping: resident templates ------------------------------------------
+    def pingtx_reserve(self, max_pings: int) -> int:
+        """Allocate the template store for max_pings pings, once per handle (include/emu_rx.h
+        emurx_pingtx_reserve); the error code is returned."""
+        return self.lib.emurx_pingtx_reserve(self.h, max_pings)
+
+    def pingtx_add(self, tmpl: bytes, icmp_off: int, vport: int) -> tuple[int, int]:
+        """A Ping's packet template into the store (emurx_pingtx_add): (error code, id)."""
+        i = C.c_uint32(0xFFFFFFFF)
+        rc = self.lib.emurx_pingtx_add(self.h, bytes(tmpl), len(tmpl), icmp_off, vport, C.byref(i))
+        return rc, int(i.value)
+
+    def pingtx_remove(self, tid: int) -> int:
+        return self.lib.emurx_pingtx_remove(self.h, tid)
+
+    def pingtx_dev(self, req, n_req: int, out, cap: int, out_desc, desc_cap: int, outcome, info, stream=None):
+        """The echo requests of n_req abi.PINGTX_REQ_DTYPE requests (device memory), generated from
+        the resident templates (include/emu_rx.h emurx_pingtx_dev): frames at 16-byte aligned
+        offsets in `out`, out_desc [desc_cap] (the descriptors tx_zmq_dev takes), outcome u8 [n_req]
+        (abi.PTX_*, or None), info u64[abi.PTX_INFO_WORDS].  The error code is returned."""
+        return self.lib.emurx_pingtx_dev(self.h, _addr(req), n_req, _addr(out), cap, _addr(out_desc), desc_cap,
+                                         _addr(outcome), _addr(info), _stream(stream))
+
+    def egress_ping_buffer(self, slot: int) -> np.ndarray:
+        """The slot's pinned request array (abi.PINGTX_REQ_DTYPE [cfg.max_frames]) as a writable view
+        (include/emu_rx.h emurx_egress_ping_buffer)."""
+        p = C.c_void_p()
+        abi.check(self.lib.emurx_egress_ping_buffer(self.h, slot, C.byref(p)), "egress_ping_buffer")
+        mf = int(self.cfg.max_frames)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(mf, 1) * 16,)).view(abi.PINGTX_REQ_DTYPE)[:mf]
+
+    def egress_submit_ping(self, slot: int, n: int, nbytes: int, n_req: int, flags: int = 0) -> int:
+        """egress_submit with the frames of the slot's first n_req requests behind the n plain frames
+        (include/emu_rx.h emurx_egress_submit_ping); the error code is returned."""
+        return self.lib.emurx_egress_submit_ping(self.h, slot, n, nbytes, flags, n_req)
+
     def respond_dev(self, frames, desc, rec, n: int, out, cap: int, out_desc, out_src, outcome, info, stream=None,
                     kinds=None, ip_time=None):
         """The ARP / ICMPv4 echo / ICMPv6 echo replies of a classified batch, built on the device
